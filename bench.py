@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: atom-frames/s of the frame-parallel RMSF path on MI355X.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -27,14 +27,20 @@ Multi-GPU, two launch forms with the same arithmetic:
     devices visible it fails, unless ``--rehearse`` (device 0 listed N
     times, in-process fold instead of RCCL; labelled in the output).
 
-At N=1 the aligned configurations are measured too ("modes": C3 = QCP
-alignment to frame 0; RMSF.py's own two-sweep "average").  Rank 0 prints ONE
-JSON line.  ``roofline`` = algorithmic bytes (12 B per atom-frame, SURVEY
-8(d)) of every timed launch of the dominant kernel / their summed duration,
-from HIP events recorded around each launch on its own stream;
-``cpu_baseline`` = the oracle's numpy restatement of RMSF.py's two sweeps on
-the host's usable cores (``mpirun -n <cores> python RMSF.py`` shape), run
-before the GPU is touched, with the unaligned (C2) sweep as a second figure.
+A plain run sets up, warms up, times the steps and prints the line; rank 0
+prints ONE JSON line.  ``roofline`` = algorithmic bytes (12 B per atom-frame,
+SURVEY 8(d)) of every timed launch of the dominant kernel / their summed
+duration, from HIP events recorded around each launch on its own stream.
+``--dump-outputs DIR`` writes what the last timed step returned (``rmsf``,
+``mean``, ``m2``, and ``average`` with --align average) as DIR/<name>.npy.
+
+``--full`` adds every measurement that takes runs of its own.  At N=1 the
+aligned configurations are measured too ("modes": C3 = QCP alignment to frame
+0; RMSF.py's own two-sweep "average"; the exact, sparse, C1, C4-share and
+C5-XTC modes), and ``cpu_baseline`` = the oracle's numpy restatement of
+RMSF.py's two sweeps on the host's usable cores (``mpirun -n <cores> python
+RMSF.py`` shape), run before the GPU is touched, with the unaligned (C2)
+sweep as a second figure.
 """
 from __future__ import annotations
 
@@ -77,6 +83,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines before the GPU is "
+                         "touched and, at N=1, the modes (see --no-cpu-baseline, --no-modes, --no-io-modes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy "
+                         "(float64; at most 64 MB in all, a fixed seeded sample of a larger array)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
     ap.add_argument("--scaling", choices=["strong", "weak"], default=None,
                     help="strong: --frames in total split over the GPUs (default); weak: --frames per GPU")
@@ -94,18 +106,18 @@ def parse(argv=None):
                          "(host-cost timing only: the merged result is not the global one)")
     ap.add_argument("--splits", type=int, default=None)
     ap.add_argument("--batch-frames", type=int, default=None, help="aligned modes: frames per superpose batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-frames", type=int, default=640,
                     help="frames per CPU process for the unaligned (C2) baseline sample")
     ap.add_argument("--cpu-average-frames", type=int, default=128,
                     help="frames per CPU process for the RMSF.py two-sweep baseline sample")
-    ap.add_argument("--no-modes", action="store_true", help="skip the aligned-mode measurements at N=1")
+    ap.add_argument("--no-modes", action="store_true", help="--full: skip the aligned-mode measurements at N=1")
     ap.add_argument("--mode-steps", type=int, default=3)
     ap.add_argument("--mode-warmup", type=int, default=3,
                     help="untimed steps before each mode's timed steps (the first 2-3 exact runs of a fresh "
                          "process are 5-15 %% slower: tools/probe_seq_bench.py)")
     ap.add_argument("--no-io-modes", action="store_true",
-                    help="N=1: skip the C4-share and C5-XTC modes (30 GB of frames, a 2.7 GB XTC file)")
+                    help="--full at N=1: skip the C4-share and C5-XTC modes (30 GB of frames, a 2.7 GB XTC file)")
     ap.add_argument("--stager-threads", type=int, default=4)
     ap.add_argument("--stager-batch", type=int, default=None, help="c5: frames per staged batch")
     ap.add_argument("--xtc-decode", choices=["gpu", "host"], default="gpu",
@@ -539,6 +551,34 @@ def sparse_selection_modes(eng, a, traj, n_atoms: int, n_total: int) -> dict:
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path: str, arrays: dict) -> list:
+    """``--dump-outputs``: every array of ``arrays`` that is not None as
+    ``path``/<name>.npy, float32 kept, everything else as float64.  All
+    files together stay within DUMP_BUDGET_BYTES: an array over its equal
+    share of the budget is written as a sample of its flattened elements at
+    sorted positions drawn once from a fixed seed (the same positions for
+    the same shape, so two runs stay comparable element for element)."""
+    import numpy as np
+
+    host = {}
+    for name, v in arrays.items():
+        if v is None:
+            continue
+        v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+        host[name] = np.ascontiguousarray(v if v.dtype == np.float32 else v.astype(np.float64))
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES - 1024 * len(host)) // max(1, len(host))  # 1 KiB each for the .npy headers
+    for name, v in host.items():
+        if v.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, share // v.itemsize, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), v)
+    return sorted(host)
+
+
 def cpu_baselines(a, wl) -> tuple[dict | None, dict | None]:
     """Before any GPU call: RMSF.py's two sweeps (the north star's ``mpirun -n
     <cores> python RMSF.py``) and the unaligned C2 sweep, both on the usable
@@ -657,6 +697,8 @@ def main_single_process(a, wl, cpu) -> None:
     sup = [c.kernel_time("superpose") for c in ctxs]
     mer = [c.kernel_time("merge") for c in ctxs]
     rmsf = ctxs[root or 0].rmsf()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"rmsf": rmsf})
     transport = ("REHEARSAL: device 0 listed %d times, %s" % (n, "no-op exchanges (host-cost timing; the merged "
                  "result is not global)" if noop else "in-process host fold") if rehearsal
                  else "RCCL via ncclCommInitAll")
@@ -711,7 +753,7 @@ def main():
 
     # -- CPU baseline first: no process has touched the GPU yet ---------------
     cpu_avg = cpu_flat = None
-    if rank == 0 and n_gpus == 1 and not a.no_cpu_baseline and not wl.get("host"):
+    if a.full and rank == 0 and n_gpus == 1 and not a.no_cpu_baseline and not wl.get("host"):
         cpu_avg, cpu_flat = cpu_baselines(a, wl)
     cpu = None
     if cpu_avg is not None:
@@ -829,6 +871,9 @@ def main():
         return dt, timer, res
 
     dt, timer, res = timed(wl["align"], a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        # what run_pipeline returned in the last timed step (the merge's root holds it)
+        dump_outputs(a.dump_outputs, {"rmsf": res.rmsf, "mean": res.mean, "m2": res.m2, "average": res.average})
     transport = "RCCL" if a.backend == "nccl" else f"{a.backend} (REHEARSAL: ranks may share a device)"
     par = (f"frame-sharded x{world} (RMSF.py:65-69 blocks), one process per GPU, {transport} Chan merge"
            if world > 1 else "1 GPU")
@@ -903,7 +948,7 @@ def main():
         out["roofline"]["note"] = "C5 is PCIe/host bound; the kernel roofline above is the device-side launches"
 
     # -- aligned modes at N=1 (reported beside the headline) ------------------
-    if world == 1 and not a.no_modes and wl["align"] is None and not wl.get("host"):
+    if a.full and world == 1 and not a.no_modes and wl["align"] is None and not wl.get("host"):
         # exact=True on the headline's frames: RMSF.py:137-138 as written
         # (k_welford_seq), bit-identical to the reference recurrence
         def run_exact(timer=None):

@@ -18,6 +18,37 @@ def test_default_is_strong_scaling_of_c2():
     assert d.mode_warmup == 3 and d.mode_steps == 3
 
 
+def test_full_is_off_by_default():
+    # a plain run measures the headline only; --full adds the CPU baselines and the modes
+    d = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert d.full is False and d.dump_outputs is None and d.steps == 7 and d.warmup == 2
+    f = bench.parse(["--full", "--dump-outputs", "x"])
+    assert f.full is True and f.dump_outputs == "x"
+
+
+def test_dump_outputs_files_and_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    arrays = {"rmsf": torch.arange(5, dtype=torch.float64), "mean": np.ones((5, 3), np.float32),
+              "m2": np.arange(6, dtype=np.int64).reshape(2, 3), "average": None}
+    assert bench.dump_outputs(str(tmp_path / "a"), arrays) == ["m2", "mean", "rmsf"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("rmsf", "mean", "m2")}
+    assert got["rmsf"].dtype == np.float64 and got["mean"].dtype == np.float32 and got["m2"].dtype == np.float64
+    assert got["mean"].shape == (5, 3) and np.array_equal(got["m2"], np.arange(6.0).reshape(2, 3))
+    assert not (tmp_path / "a" / "average.npy").exists()
+    assert bench.DUMP_BUDGET_BYTES <= 64e6
+    # over the budget: the same seeded sample of the flattened array each time, the files within the budget
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096 + 2 * 1024)
+    big = {"a": np.arange(3000, dtype=np.float64).reshape(1000, 3), "b": np.arange(10, dtype=np.float64)}
+    for sub in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / sub), big)
+    a1, a2 = np.load(tmp_path / "b1" / "a.npy"), np.load(tmp_path / "b2" / "a.npy")
+    assert a1.shape == (256,) and np.array_equal(a1, a2) and np.all(np.diff(a1) > 0)
+    assert np.array_equal(np.load(tmp_path / "b1" / "b.npy"), big["b"])
+    assert sum(p.stat().st_size for p in (tmp_path / "b1").iterdir()) <= 4096 + 2 * 1024
+
+
 def test_weak_scaling_and_c4():
     wl = bench.resolve(bench.parse(["--scaling", "weak"]), 4)
     assert wl["scaling"] == "weak" and wl["n_total"] == 80_000

@@ -61,8 +61,8 @@ def test_io_modes_small(capsys):
 
 
 def test_bench_cli_small_json_line():
-    cmd = [sys.executable, "bench.py", "--n-atoms", "20000", "--frames", "300", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--mode-steps", "1", "--no-io-modes"]
+    cmd = [sys.executable, "bench.py", "--full", "--n-atoms", "20000", "--frames", "300", "--steps", "3",
+           "--warmup", "1", "--no-cpu-baseline", "--mode-steps", "1", "--no-io-modes"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -79,6 +79,37 @@ def test_bench_cli_small_json_line():
     x = m["c2_exact"]
     assert x["kernel"] == "k_welford_seq" and 0 < x["hbm_frac"] < 1.0
     assert x["max_abs_rmsf_diff_vs_headline"] < 1e-12
+
+
+@pytest.mark.parametrize("align", ["none", "average"])
+def test_plain_run_is_lean_and_dumps_the_last_step(align, tmp_path):
+    """Without ``--full`` the line holds the headline only (no modes, no CPU
+    baseline), and ``--dump-outputs`` writes what the last timed step
+    returned: float64 arrays of the inputs the seed fixes, the oracle's RMSF
+    to 1e-6 A (the frame-parallel path's bound) and the line's checksum."""
+    d = tmp_path / "out"
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--n-atoms", "1501", "--frames", "300", "--steps", "2",
+           "--warmup", "1", "--align", align, "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert "modes" not in line and line["cpu_baseline"] is None
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["roofline"]["launches"] == 2 * (1 + (align != "none"))
+    assert line["value"] == pytest.approx(1501 * 300 / (line["ms_per_step"] / 1e3))
+    names = {"rmsf": (1501,), "mean": (1501, 3), "m2": (1501, 3)}
+    if align == "average":
+        names.update(average=(1501, 3))
+    assert sorted(p.name for p in d.iterdir()) == sorted(n + ".npy" for n in names)
+    got = {n: np.load(d / (n + ".npy")) for n in names}
+    for n, shape in names.items():
+        assert got[n].dtype == np.float64 and got[n].shape == shape and np.isfinite(got[n]).all()
+    assert float(got["rmsf"].sum()) == pytest.approx(line["rmsf_checksum"], rel=1e-14)
+    from rmsf_amd.synth import motion_table
+
+    mt = motion_table(1, 300) if align != "none" else None
+    traj = SY.frames(0, 1501, 0, 300, mt)
+    exp = O.rmsf_script(traj, None, None, size=1, align=None if align == "none" else align)
+    assert np.abs(got["rmsf"] - exp["rmsf"]).max() < 1e-6
 
 
 def test_bench_batched_launches_roofline_below_peak():

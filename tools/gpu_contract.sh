@@ -16,5 +16,5 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 tail -1 $O/tests.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 500 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 500 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/bench.json')); print(d['ms_per_step'], d['roofline']['frac'], {k: (v.get('ms_per_step') if isinstance(v, dict) else v) for k, v in d.get('modes', {}).items()})"
