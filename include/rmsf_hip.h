@@ -632,15 +632,30 @@ int rmsf_xtc_frame_record(const rmsf_xtc *x, int64_t frame, int64_t *offset,
  * threads), copied to HBM on the slot's own stream and decompressed there,
  * one wave per frame (the xdr3dfcoord stream of a frame is sequential;
  * frames run in parallel), into float32 [n][n_atoms][3] Angstrom frames,
- * bit-identical to rmsf_xtc_read().  The selection is applied downstream
- * (rmsf_accumulate / rmsf_superpose gather it in-kernel).  Replaces the
- * libxdrfile decode behind trajectory[frame] (RMSF.py:92,124).           */
+ * bit-identical to rmsf_xtc_read().  Replaces the libxdrfile decode behind
+ * trajectory[frame] (RMSF.py:92,124).
+ * A decoder from rmsf_xtcdec_create writes every atom, and the selection is
+ * applied downstream (rmsf_accumulate / rmsf_superpose gather it in-kernel).
+ * One from rmsf_xtcdec_create_sel writes the selected atoms only: compact
+ * float32 [n][n_sel][3] frames in the selection's order, rmsf_xtc_read(h_sel)'s
+ * bits, ready for the kernels' contiguous path (d_sel = NULL).  Below,
+ * "rows" is n_atoms for the former and n_sel for the latter.              */
 typedef struct rmsf_xtcdec rmsf_xtcdec;
 int rmsf_xtcdec_create(const rmsf_xtc *x, int64_t batch_frames, int n_slots,
                        int n_threads, rmsf_xtcdec **out);
+/* A decoder of the atoms h_sel[0..n_sel) only (any order, each index once:
+ * RMSF_EINVAL for a duplicate, which has no single output row, or an index
+ * outside the file's atoms).  RMSF.py reads every atom of every frame and
+ * keeps 214 CA atoms of 47,681 (RMSF.py:77,92,124,126); here the other
+ * atoms are never written: the slots' frame buffers are
+ * batch_frames * n_sel * 12 bytes.  The device map of the selection is
+ * built once, on the current device.                                       */
+int rmsf_xtcdec_create_sel(const rmsf_xtc *x, int64_t batch_frames,
+                           int n_slots, int n_threads, const int32_t *h_sel,
+                           int64_t n_sel, rmsf_xtcdec **out);
 int rmsf_xtcdec_destroy(rmsf_xtcdec *d);
 /* Decode frames f0, f0+step, ... (n_frames <= batch_frames) into the next
- * slot; *d_frames = its device frames (frame stride 3*n_atoms floats).
+ * slot; *d_frames = its device frames (frame stride 3*rows floats).
  * consumer_stream waits for the decode.  Per-frame errors (corrupt data:
  * the frame is filled with NaN) are reported when the slot is next used or
  * by rmsf_xtcdec_synchronize().                                             */
@@ -649,13 +664,14 @@ int rmsf_xtcdec_decode(rmsf_xtcdec *d, int64_t f0, int64_t n_frames,
                        float **d_frames);
 /* Decode the n_frames frames h_frames[0..n) (any order, repeats allowed;
  * n_frames <= batch_frames) into the next slot, frame k of the list at
- * *d_frames + k*3*n_atoms: a run(frames=...) list of scattered frames costs
+ * *d_frames + k*3*rows: a run(frames=...) list of scattered frames costs
  * one batched read + decode instead of one per frame.                      */
 int rmsf_xtcdec_decode_list(rmsf_xtcdec *d, const int64_t *h_frames,
                             int64_t n_frames, void *consumer_stream, int *slot,
                             float **d_frames);
 /* The same into the caller's device buffer: frame k of the batch at
- * d_out + k*out_stride floats (e.g. a trajectory kept resident in HBM). */
+ * d_out + k*out_stride floats, out_stride >= 3*rows (e.g. a trajectory kept
+ * resident in HBM).                                                         */
 int rmsf_xtcdec_decode_into(rmsf_xtcdec *d, int64_t f0, int64_t n_frames,
                             int64_t step, float *d_out, int64_t out_stride,
                             void *consumer_stream, int *slot);
@@ -676,6 +692,29 @@ int rmsf_xtc_decode_records_host(const void *h_records,
                                  const int64_t *h_rec_len, int64_t n_frames,
                                  int64_t n_atoms, float *h_out,
                                  int64_t out_stride, int32_t *h_status);
+/* Kernel level, selected atoms only (the positions RMSF.py:92,124 read and
+ * RMSF.py:77,126 then cut down to the CA atoms): d_row_of_atom[n_atoms] holds
+ * each atom's output row in [0, n_sel), or -1; frame f's selected atoms go
+ * to d_out + f*out_stride + 3*row (out_stride >= 3*n_sel) and nothing else
+ * is written.  A corrupt frame's n_sel rows are filled with NaN.  The map
+ * is trusted (as the record table is): every row must be < n_sel.         */
+int rmsf_xtc_decode_records_sel(const void *d_records,
+                                const int64_t *d_rec_off,
+                                const int64_t *d_rec_len, int64_t n_frames,
+                                int64_t n_atoms, const int32_t *d_row_of_atom,
+                                int64_t n_sel, float *d_out,
+                                int64_t out_stride, int32_t *d_status,
+                                void *stream);
+/* The same code run on the host (the CPU tier of the tests; no HIP calls:
+ * what RMSF.py:77,92,124,126 keep of a frame, without a device).  Checks
+ * the map's entries.                                                       */
+int rmsf_xtc_decode_records_sel_host(const void *h_records,
+                                     const int64_t *h_rec_off,
+                                     const int64_t *h_rec_len,
+                                     int64_t n_frames, int64_t n_atoms,
+                                     const int32_t *h_row_of_atom,
+                                     int64_t n_sel, float *h_out,
+                                     int64_t out_stride, int32_t *h_status);
 
 /* ---- RMSF context: the whole per-rank loop behind one opaque handle -------
  * SURVEY.md 8(b)'s minimal export set, for hosts that bring neither torch
@@ -794,6 +833,9 @@ int rmsf_push_frames(rmsf_ctx *ctx, const float *xyz, int64_t n_frames,
 /* Push XTC frames f0, f0+step, ... (n_frames) of an open file (RMSF.py:92,124
  * frame source): the compressed records are decompressed on the GPU (the
  * context keeps an rmsf_xtcdec for the file, up to 3 batches in flight).
+ * When the context's selection is a proper subset of the atoms with no
+ * index listed twice, only the selected atoms are decoded
+ * (rmsf_xtcdec_create_sel); otherwise whole frames, gathered in-kernel.
  * Synchronises at the end to report corrupt frames.                          */
 int rmsf_push_xtc(rmsf_ctx *ctx, const rmsf_xtc *x, int64_t f0,
                   int64_t n_frames, int64_t step, int mode);

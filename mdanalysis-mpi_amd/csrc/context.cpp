@@ -275,6 +275,7 @@ struct rmsf_ctx {
   rmsf_stager *stager = nullptr;
   rmsf_xtcdec *xdec = nullptr;  // GPU XTC decoder, bound to the file of serial xdec_serial
   uint64_t xdec_serial = 0;
+  bool xdec_sel = false;  // xdec decodes the selected atoms only (compact frames)
   int64_t stage_batch = 0;  // 0 = auto
   int stage_slots = 2, stage_threads = 4;
   bool stager_dirty = true;
@@ -1607,12 +1608,37 @@ RMSF_EXPORT int rmsf_push_frames(rmsf_ctx *c, const float *xyz, int64_t n_frames
 namespace {
 
 // The context's GPU XTC decoder for file x (made on first use, remade for another file).
+// When the selection is a proper subset of the atoms with no index listed
+// twice, the decoder writes the selected atoms only (c->xdec_sel: compact
+// frames of n_sel rows); the selection is fixed at rmsf_ctx_create, so only
+// another file remakes it.  The caller holds the context's DeviceScope: the
+// decoder's device memory (slots, selection map) lives on c->dev.
 int ensure_xdec(rmsf_ctx *c, const rmsf_xtc *x, int n_slots, int64_t *batch) {
   *batch = std::max<int64_t>(1, std::min<int64_t>(4096, (int64_t(2) << 30) / (12 * c->n_atoms)));
   if (!c->xdec || c->xdec_serial != x->serial) {
     if (c->xdec) CX_OK(rmsf_xtcdec_destroy(c->xdec));
     c->xdec = nullptr;
-    CX_OK(rmsf_xtcdec_create(x, *batch, n_slots, 16, &c->xdec));
+    c->xdec_sel = false;
+    std::vector<int32_t> sel;
+    if (c->n_sel < c->n_atoms) {
+      sel = c->h_sel;
+      if (sel.empty())  // atoms 0..n_sel-1
+        for (int64_t a = 0; a < c->n_sel; ++a) sel.push_back((int32_t)a);
+      std::vector<char> seen((size_t)c->n_atoms, 0);
+      for (int32_t a : sel) {
+        if (seen[a]) {  // a duplicate has no single output row: whole frames, gathered
+          sel.clear();
+          break;
+        }
+        seen[a] = 1;
+      }
+    }
+    if (!sel.empty()) {
+      CX_OK(rmsf_xtcdec_create_sel(x, *batch, n_slots, 16, sel.data(), (int64_t)sel.size(), &c->xdec));
+      c->xdec_sel = true;
+    } else {
+      CX_OK(rmsf_xtcdec_create(x, *batch, n_slots, 16, &c->xdec));
+    }
     c->xdec_serial = x->serial;
   }
   return RMSF_OK;
@@ -1633,7 +1659,8 @@ int push_decoded(rmsf_ctx *c, int64_t n_frames, int64_t batch, int mode, Decode 
   size_t head = 0;
   auto consume = [&]() -> int {
     const Pending p = q[head++];
-    const int rc = process(c, p.d, 3 * c->n_atoms, p.n, c->d_sel(), mode);
+    const int rc = c->xdec_sel ? process(c, p.d, 3 * c->n_sel, p.n, nullptr, mode)
+                               : process(c, p.d, 3 * c->n_atoms, p.n, c->d_sel(), mode);
     const int rc2 = rmsf_xtcdec_release(c->xdec, p.slot, c->stream);
     return rc ? rc : rc2;
   };
@@ -1659,8 +1686,9 @@ RMSF_EXPORT int rmsf_push_xtc(rmsf_ctx *c, const rmsf_xtc *x, int64_t f0, int64_
   if (x->n_atoms != c->n_atoms) return fail(RMSF_EINVAL, "rmsf_push_xtc: the file's atom count differs");
   DeviceScope ds(c->dev);
   CX_OK(flush_slab(c));
-  // the records are decompressed on the GPU (csrc/xtc_gpu.hip) into full
-  // frames; the accumulate kernels gather the selection
+  // the records are decompressed on the GPU (csrc/xtc_gpu.hip): the selected
+  // atoms only where the selection allows it (ensure_xdec), else full frames
+  // whose selection the accumulate kernels gather
   int64_t batch = 0;
   CX_OK(ensure_xdec(c, x, 3, &batch));
   return push_decoded(c, n_frames, batch, mode, [&](int64_t i, int64_t n, int *slot, float **d) {

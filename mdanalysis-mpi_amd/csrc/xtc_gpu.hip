@@ -11,9 +11,16 @@
 // a wave-uniform walk that reads just the 1-6 flag bits per atom group, and
 // a lane-parallel decode of 64 recorded groups at a time.  Output: float32
 // [n][n_atoms][3] Angstrom frames in HBM with MDAnalysis' rounding
-// f32(f32(int * f32(1/prec)) * 10), bit-identical to the host decoder.  The
-// selection is applied downstream (the accumulate kernels gather it
-// in-kernel), as for any HBM-resident trajectory.
+// f32(f32(int * f32(1/prec)) * 10), bit-identical to the host decoder.
+//
+// Without a selection every atom is written and the selection is applied
+// downstream (the accumulate kernels gather it in-kernel), as for any
+// HBM-resident trajectory.  With one (the *_sel entries: RMSF.py keeps 214 CA
+// atoms of 47,681, RMSF.py:77,92,124,126) pass 2 writes the selected atoms
+// only, as compact [n][n_sel][3] frames in the selection's order, through a
+// device map atom -> output row (see "output rows" below): a group with no
+// selected atom extracts no triple and a run stops after its last selected
+// atom.  Pass 1 still walks every group, since the bit offsets are sequential.
 //
 // Packed triples of <= 52 bits are split with two exact double-precision
 // divisions (quotient estimate by reciprocal, one correction step); wider
@@ -297,18 +304,57 @@ __host__ __device__ inline void triple_at(const XtcFrame &F, const Src &src, int
   }
 }
 
-__host__ __device__ inline void put_atom(float *o, int64_t idx, int c0, int c1, int c2, float invp) {
+// ---- output rows ---------------------------------------------------------------
+// Where pass 2 writes an atom.  AllRows: atom a at row a, every atom (the
+// code without a selection, unchanged).  MapRows: row_of_atom[a] (int32
+// [n_atoms]) is the output row of a selected atom, -1 otherwise, the rows
+// being in the selection's order.
+struct AllRows {
+  static constexpr bool kAll = true;
+  __host__ __device__ inline int64_t row(int64_t atom) const { return atom; }
+};
+struct MapRows {
+  static constexpr bool kAll = false;
+  const int32_t *row_of_atom;
+  __host__ __device__ inline int64_t row(int64_t atom) const { return row_of_atom[atom]; }
+  // Small triples a group of atoms [idx, idx + nsmall] must decode: -1 when
+  // none of its atoms is selected (the group is skipped), else up to its
+  // last selected atom -- a small triple chains on the one before it, so
+  // nothing before the last can be skipped.  Atom idx is small triple 0,
+  // atom idx + 1 the large triple (the writer's swap), atom idx + 1 + k
+  // small triple k.
+  __host__ __device__ inline int triples(int idx, int nsmall) const {
+    int last = -1;
+    for (int k = 0; k <= nsmall; ++k) last = row_of_atom[idx + k] >= 0 ? k : last;
+    if (last < 0) return -1;
+    if (nsmall == 0) return 0;
+    if (last >= 2) return last;
+    return last == 1 && row_of_atom[idx] < 0 ? 0 : 1;
+  }
+};
+
+template <class Rows>
+__host__ __device__ inline void put_atom(const Rows &rows, float *o, int64_t idx, int c0, int c1, int c2,
+                                         float invp) {
+  const int64_t r = rows.row(idx);
+  if constexpr (!Rows::kAll)
+    if (r < 0) return;
   float a, b, c;
   to_angstrom(c0, c1, c2, invp, a, b, c);
-  o[3 * idx] = a;
-  o[3 * idx + 1] = b;
-  o[3 * idx + 2] = c;
+  o[3 * r] = a;
+  o[3 * r + 1] = b;
+  o[3 * r + 2] = c;
 }
 
 // pass 2: one group
-template <class Src>
+template <class Src, class Rows>
 __host__ __device__ inline void decode_group(const XtcFrame &F, const XtcGroup &g, const int *magic,
-                                             const double *inv_magic, float *o, const Src &src) {
+                                             const double *inv_magic, float *o, const Src &src, const Rows &rows) {
+  int ntrip = g.nsmall();
+  if constexpr (!Rows::kAll) {
+    ntrip = rows.triples(g.idx, ntrip);
+    if (ntrip < 0) return;
+  }
   int cur[3];
   if (F.bitsize == 0) {
     int64_t p = g.pos;
@@ -323,8 +369,14 @@ __host__ __device__ inline void decode_group(const XtcFrame &F, const XtcGroup &
   for (int c = 0; c < 3; ++c) cur[c] += F.minint[c];
   const int nsmall = g.nsmall(), sidx = g.sidx();
   if (nsmall == 0) {
-    put_atom(o, g.idx, cur[0], cur[1], cur[2], F.inv_precision);
+    put_atom(rows, o, g.idx, cur[0], cur[1], cur[2], F.inv_precision);
     return;
+  }
+  if constexpr (!Rows::kAll) {
+    if (ntrip == 0) {  // of the run only the swapped large atom is selected
+      put_atom(rows, o, g.idx + 1, cur[0], cur[1], cur[2], F.inv_precision);
+      return;
+    }
   }
   const unsigned m = (unsigned)magic[sidx];
   const unsigned ss[3] = {m, m, m};
@@ -333,16 +385,16 @@ __host__ __device__ inline void decode_group(const XtcFrame &F, const XtcGroup &
   const int smallnum = magic[sidx] / 2;
   int prev[3] = {cur[0], cur[1], cur[2]};
   int64_t p = g.pos + F.large_bits + g.fbits();
-  for (int k = 0; k < nsmall; ++k) {
+  for (int k = 0; k < ntrip; ++k) {
     int t[3];
     triple_at(F, src, p, sidx, ss, is, t);
     p += sidx;
     for (int c = 0; c < 3; ++c) t[c] += prev[c] - smallnum;
     if (k == 0) {  // the writer swapped the first two atoms (water)
-      put_atom(o, g.idx, t[0], t[1], t[2], F.inv_precision);
-      put_atom(o, g.idx + 1, prev[0], prev[1], prev[2], F.inv_precision);
+      put_atom(rows, o, g.idx, t[0], t[1], t[2], F.inv_precision);
+      put_atom(rows, o, g.idx + 1, prev[0], prev[1], prev[2], F.inv_precision);
     } else {
-      put_atom(o, g.idx + 1 + k, t[0], t[1], t[2], F.inv_precision);
+      put_atom(rows, o, g.idx + 1 + k, t[0], t[1], t[2], F.inv_precision);
     }
     prev[0] = t[0];
     prev[1] = t[1];
@@ -353,8 +405,9 @@ __host__ __device__ inline void decode_group(const XtcFrame &F, const XtcGroup &
 // Frame header of one XTC record (starting at its magic word, `words`
 // long): the raw form (<= 9 atoms) is decoded here (*raw = true); otherwise
 // F describes the compressed stream.  Mirrors decode_coords() of xtc.cpp.
+template <class Rows>
 __host__ __device__ inline int32_t parse_header(const uint32_t *rec, int64_t words, int64_t n_atoms, float *o,
-                                                XtcFrame &F, bool *raw) {
+                                                XtcFrame &F, bool *raw, const Rows &rows) {
 #pragma clang fp contract(off)
   *raw = false;
   if (words < 14) return kShort;
@@ -365,8 +418,12 @@ __host__ __device__ inline int32_t parse_header(const uint32_t *rec, int64_t wor
   int64_t left = words - 14;
   if (natoms <= 9) {
     if (left < 3 * natoms) return kShort;
-    for (int a = 0; a < natoms; ++a)  // raw floats (nm) x 10, as MDAnalysis
-      for (int c = 0; c < 3; ++c) o[3 * a + c] = f32_bits(be32w(p[3 * a + c])) * 10.0f;
+    for (int a = 0; a < natoms; ++a) {  // raw floats (nm) x 10, as MDAnalysis
+      const int r = (int)rows.row(a);
+      if constexpr (!Rows::kAll)
+        if (r < 0) continue;
+      for (int c = 0; c < 3; ++c) o[3 * r + c] = f32_bits(be32w(p[3 * a + c])) * 10.0f;
+    }
     *raw = true;
     return kOk;
   }
@@ -432,7 +489,8 @@ __host__ __device__ inline bool group_step(const XtcFrame &F, const int *magic, 
 }
 
 // host: pass 1 and pass 2 interleaved group by group
-inline int32_t scan_host(const XtcFrame &F, const int *magic, const double *inv, float *o) {
+template <class Rows>
+inline int32_t scan_host(const XtcFrame &F, const int *magic, const double *inv, float *o, const Rows &rows) {
   const MemSrc src{F.s, F.nw};
   MemWindow b;
   b.start(F.s, F.nw);
@@ -447,7 +505,7 @@ inline int32_t scan_host(const XtcFrame &F, const int *magic, const double *inv,
     if (!group_step(F, magic, p6, i, run, sidx, adv, g.meta)) return kCorrupt;
     b.advance(adv);
     if (b.consumed() > F.nbits) return kCorrupt;
-    decode_group(F, g, magic, inv, o, src);
+    decode_group(F, g, magic, inv, o, src, rows);
   }
   return kOk;
 }
@@ -500,8 +558,9 @@ struct RingFill {
 // stream) the sequential step: a 6-bit peek and group_step(), exactly as on
 // the host.  Group k of a batch of 64 lives in lane k; a full batch is
 // decoded lane-parallel (pass 2) from the LDS ring.
-__device__ int32_t scan_wave(const XtcFrame &F, const int *magic, const double *inv, float *o,
-                             uint32_t *ring) {
+template <class Rows>
+__device__ int32_t scan_wave(const XtcFrame &F, const int *magic, const double *inv, float *o, uint32_t *ring,
+                             const Rows &rows) {
   const int lane = (int)(threadIdx.x & 63);
   RingFill rf{F.s, F.nw, ring, lane, 0, {}};
   rf.issue();
@@ -514,7 +573,7 @@ __device__ int32_t scan_wave(const XtcFrame &F, const int *magic, const double *
       g.pos = (int64_t)((uint64_t)r_hi << 32 | r_lo);
       g.idx = (int32_t)r_idx;
       g.meta = r_meta;
-      decode_group(F, g, magic, inv, o, src);
+      decode_group(F, g, magic, inv, o, src, rows);
     }
   };
   auto rd = [&](int64_t j) { return (uint32_t)uni((int)ring[j & (kRing - 1)]); };
@@ -606,10 +665,34 @@ __global__ __launch_bounds__(64) void k_xtc_decode(const uint32_t *__restrict__ 
   float *o = out + f * out_stride;
   XtcFrame F;
   bool raw;
-  int32_t st = parse_header(words + rec_off[f], rec_len[f], n_atoms, o, F, &raw);
-  if (st == kOk && !raw) st = scan_wave(F, g_magic.v, g_inv.v, o, ring);
+  const AllRows rows{};
+  int32_t st = parse_header(words + rec_off[f], rec_len[f], n_atoms, o, F, &raw, rows);
+  if (st == kOk && !raw) st = scan_wave(F, g_magic.v, g_inv.v, o, ring, rows);
   if (st != kOk) {
     for (int64_t k = threadIdx.x; k < 3 * n_atoms; k += 64) o[k] = __builtin_nanf("");
+  }
+  if (threadIdx.x == 0) status[f] = st;
+}
+
+// The same writing only the selected atoms: row_of_atom[n_atoms] (output row
+// or -1), n_sel rows per frame.  (Its own kernel, not a shared template
+// body: k_xtc_decode above compiles to the ISA it had before this existed.)
+__global__ __launch_bounds__(64) void k_xtc_decode_sel(const uint32_t *__restrict__ words,
+                                                       const int64_t *__restrict__ rec_off,
+                                                       const int64_t *__restrict__ rec_len, int64_t n_atoms,
+                                                       const int32_t *__restrict__ row_of_atom, int64_t n_sel,
+                                                       float *__restrict__ out, int64_t out_stride,
+                                                       int32_t *__restrict__ status) {
+  __shared__ uint32_t ring[kRing];
+  const int64_t f = blockIdx.x;
+  float *o = out + f * out_stride;
+  XtcFrame F;
+  bool raw;
+  const MapRows rows{row_of_atom};
+  int32_t st = parse_header(words + rec_off[f], rec_len[f], n_atoms, o, F, &raw, rows);
+  if (st == kOk && !raw) st = scan_wave(F, g_magic.v, g_inv.v, o, ring, rows);
+  if (st != kOk) {  // the frame's n_sel rows and never more
+    for (int64_t k = threadIdx.x; k < 3 * n_sel; k += 64) o[k] = __builtin_nanf("");
   }
   if (threadIdx.x == 0) status[f] = st;
 }
@@ -714,6 +797,8 @@ struct PoolWait {
 struct rmsf_xtcdec {
   const rmsf_xtc *x = nullptr;
   int64_t batch = 0, n_atoms = 0;
+  int64_t n_rows = 0;                // rows per decoded frame: n_atoms, or n_sel with a selection
+  int32_t *d_row_of_atom = nullptr;  // rmsf_xtcdec_create_sel: the selection's device map
   int n_threads = 1;
   std::unique_ptr<ReadPool> pool;
   struct Slot {
@@ -765,6 +850,10 @@ void free_slot(rmsf_xtcdec::Slot &s) {
   s = rmsf_xtcdec::Slot{};
 }
 
+// row_of_atom != nullptr: a decoder of the selected atoms (its map, [n_atoms])
+int xtcdec_create(const rmsf_xtc *x, int64_t batch_frames, int n_slots, int n_threads,
+                  const std::vector<int32_t> *row_of_atom, rmsf_xtcdec **out);
+
 }  // namespace
 
 extern "C" {
@@ -796,8 +885,52 @@ RMSF_EXPORT int rmsf_xtc_decode_records_host(const void *h_records, const int64_
     float *o = h_out + f * out_stride;
     XtcFrame F;
     bool raw;
-    int32_t st = parse_header(w + h_rec_off[f], h_rec_len[f], n_atoms, o, F, &raw);
-    if (st == kOk && !raw) st = scan_host(F, h_magic.v, h_inv.v, o);
+    const AllRows rows{};
+    int32_t st = parse_header(w + h_rec_off[f], h_rec_len[f], n_atoms, o, F, &raw, rows);
+    if (st == kOk && !raw) st = scan_host(F, h_magic.v, h_inv.v, o, rows);
+    h_status[f] = st;
+  }
+  return RMSF_OK;
+}
+
+RMSF_EXPORT int rmsf_xtc_decode_records_sel(const void *d_records, const int64_t *d_rec_off,
+                                            const int64_t *d_rec_len, int64_t n_frames, int64_t n_atoms,
+                                            const int32_t *d_row_of_atom, int64_t n_sel, float *d_out,
+                                            int64_t out_stride, int32_t *d_status, void *stream) {
+  if (!d_records || !d_rec_off || !d_rec_len || !d_row_of_atom || !d_out || !d_status || n_frames < 0 ||
+      n_atoms < 1 || n_sel < 1 || n_sel > n_atoms || out_stride < 3 * n_sel ||
+      (reinterpret_cast<uintptr_t>(d_records) & 3))
+    return fail(RMSF_EINVAL, "rmsf_xtc_decode_records_sel: bad arguments");
+  if (n_frames == 0) return RMSF_OK;
+  if (n_frames > 0x7fffffffLL) return fail(RMSF_EINVAL, "rmsf_xtc_decode_records_sel: too many frames");
+  hipLaunchKernelGGL(k_xtc_decode_sel, dim3((unsigned)n_frames), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                     static_cast<const uint32_t *>(d_records), d_rec_off, d_rec_len, n_atoms, d_row_of_atom, n_sel,
+                     d_out, out_stride, d_status);
+  XD_HIP(hipGetLastError());
+  return RMSF_OK;
+}
+
+RMSF_EXPORT int rmsf_xtc_decode_records_sel_host(const void *h_records, const int64_t *h_rec_off,
+                                                 const int64_t *h_rec_len, int64_t n_frames, int64_t n_atoms,
+                                                 const int32_t *h_row_of_atom, int64_t n_sel, float *h_out,
+                                                 int64_t out_stride, int32_t *h_status) {
+  if (!h_records || !h_rec_off || !h_rec_len || !h_row_of_atom || !h_out || !h_status || n_frames < 0 ||
+      n_atoms < 1 || n_sel < 1 || n_sel > n_atoms || out_stride < 3 * n_sel ||
+      (reinterpret_cast<uintptr_t>(h_records) & 3))
+    return fail(RMSF_EINVAL, "rmsf_xtc_decode_records_sel_host: bad arguments");
+  for (int64_t a = 0; a < n_atoms; ++a)  // the device entry trusts its map; here the check is cheap
+    if (h_row_of_atom[a] < -1 || h_row_of_atom[a] >= n_sel)
+      return fail(RMSF_EINVAL, "rmsf_xtc_decode_records_sel_host: map entry out of range");
+  const uint32_t *w = static_cast<const uint32_t *>(h_records);
+  const MapRows rows{h_row_of_atom};
+  for (int64_t f = 0; f < n_frames; ++f) {
+    float *o = h_out + f * out_stride;
+    XtcFrame F;
+    bool raw;
+    int32_t st = parse_header(w + h_rec_off[f], h_rec_len[f], n_atoms, o, F, &raw, rows);
+    if (st == kOk && !raw) st = scan_host(F, h_magic.v, h_inv.v, o, rows);
+    if (st != kOk)  // as the kernel: a corrupt frame's n_sel rows are NaN
+      for (int64_t k = 0; k < 3 * n_sel; ++k) o[k] = __builtin_nanf("");
     h_status[f] = st;
   }
   return RMSF_OK;
@@ -807,12 +940,51 @@ RMSF_EXPORT int rmsf_xtcdec_create(const rmsf_xtc *x, int64_t batch_frames, int 
                                    rmsf_xtcdec **out) {
   if (!x || !out || batch_frames < 1 || n_slots < 1 || n_slots > 16 || n_threads < 1)
     return fail(RMSF_EINVAL, "rmsf_xtcdec_create: bad arguments");
+  return xtcdec_create(x, batch_frames, n_slots, n_threads, nullptr, out);
+}
+
+RMSF_EXPORT int rmsf_xtcdec_create_sel(const rmsf_xtc *x, int64_t batch_frames, int n_slots, int n_threads,
+                                       const int32_t *h_sel, int64_t n_sel, rmsf_xtcdec **out) {
+  if (!x || !out || !h_sel || n_sel < 1 || batch_frames < 1 || n_slots < 1 || n_slots > 16 || n_threads < 1)
+    return fail(RMSF_EINVAL, "rmsf_xtcdec_create_sel: bad arguments");
+  *out = nullptr;
+  // atom -> output row, -1 = not selected; a duplicate has no single row
+  std::vector<int32_t> map((size_t)x->n_atoms, -1);
+  for (int64_t r = 0; r < n_sel; ++r) {
+    const int64_t a = h_sel[r];
+    if (a < 0 || a >= x->n_atoms)
+      return fail(RMSF_EINVAL, "rmsf_xtcdec_create_sel: selection index " + std::to_string(a) + " out of range");
+    if (map[a] >= 0)
+      return fail(RMSF_EINVAL, "rmsf_xtcdec_create_sel: selection index " + std::to_string(a) + " listed twice");
+    map[a] = (int32_t)r;
+  }
+  return xtcdec_create(x, batch_frames, n_slots, n_threads, &map, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+int xtcdec_create(const rmsf_xtc *x, int64_t batch_frames, int n_slots, int n_threads,
+                  const std::vector<int32_t> *row_of_atom, rmsf_xtcdec **out) {
   *out = nullptr;
   auto *d = new rmsf_xtcdec();
   d->x = x;
   d->batch = batch_frames;
   d->n_atoms = x->n_atoms;
+  d->n_rows = x->n_atoms;
   d->n_threads = n_threads;
+  if (row_of_atom) {  // on the caller's current device, as the slots below
+    d->n_rows = (int64_t)std::count_if(row_of_atom->begin(), row_of_atom->end(), [](int32_t r) { return r >= 0; });
+    const size_t bytes = row_of_atom->size() * sizeof(int32_t);
+    hipError_t e = hipMalloc((void **)&d->d_row_of_atom, bytes);
+    if (e == hipSuccess) e = hipMemcpy(d->d_row_of_atom, row_of_atom->data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      if (d->d_row_of_atom) (void)hipFree(d->d_row_of_atom);
+      delete d;
+      return fail(RMSF_ENOMEM, std::string("rmsf_xtcdec_create_sel: ") + hipGetErrorString(e));
+    }
+  }
   // read threads on the GPU's NUMA node when it is known
   int dev = 0;
   cpu_set_t near;
@@ -835,6 +1007,7 @@ RMSF_EXPORT int rmsf_xtcdec_create(const rmsf_xtc *x, int64_t batch_frames, int 
     if (e == hipSuccess) e = hipEventRecord(s.done, s.s);
     if (e != hipSuccess) {
       for (auto &t : d->slots) free_slot(t);
+      if (d->d_row_of_atom) (void)hipFree(d->d_row_of_atom);
       delete d;
       return fail(RMSF_ENOMEM, std::string("rmsf_xtcdec_create: ") + hipGetErrorString(e));
     }
@@ -843,9 +1016,14 @@ RMSF_EXPORT int rmsf_xtcdec_create(const rmsf_xtc *x, int64_t batch_frames, int 
   return RMSF_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
 RMSF_EXPORT int rmsf_xtcdec_destroy(rmsf_xtcdec *d) {
   if (d) {
     for (auto &s : d->slots) free_slot(s);
+    if (d->d_row_of_atom) (void)hipFree(d->d_row_of_atom);
     delete d;
   }
   return RMSF_OK;
@@ -932,16 +1110,19 @@ int xtcdec_decode(rmsf_xtcdec *d, int64_t f0, int64_t n, int64_t step, float *ou
   XD_HIP(hipMemcpyAsync(s.d_tab, s.h_tab, 2 * d->batch * sizeof(int64_t), hipMemcpyHostToDevice, s.s));
   if (!out) {
     if (!s.d_frames) {
-      const size_t bytes = (size_t)d->batch * 3 * (size_t)d->n_atoms * sizeof(float);
+      const size_t bytes = (size_t)d->batch * 3 * (size_t)d->n_rows * sizeof(float);
       hipError_t e = hipMalloc((void **)&s.d_frames, bytes);
       if (e != hipSuccess) return fail(RMSF_ENOMEM, std::string("rmsf_xtcdec_decode: ") + hipGetErrorString(e));
     }
     XD_HIP(hipStreamWaitEvent(s.s, s.released, 0));  // the consumer is done with the previous frames
     out = s.d_frames;
-    out_stride = 3 * d->n_atoms;
+    out_stride = 3 * d->n_rows;
   }
-  rc = rmsf_xtc_decode_records(s.d_raw, s.d_tab, s.d_tab + d->batch, n, d->n_atoms, out, out_stride, s.d_status,
-                               s.s);
+  rc = d->d_row_of_atom
+           ? rmsf_xtc_decode_records_sel(s.d_raw, s.d_tab, s.d_tab + d->batch, n, d->n_atoms, d->d_row_of_atom,
+                                         d->n_rows, out, out_stride, s.d_status, s.s)
+           : rmsf_xtc_decode_records(s.d_raw, s.d_tab, s.d_tab + d->batch, n, d->n_atoms, out, out_stride,
+                                     s.d_status, s.s);
   if (rc) return rc;
   XD_HIP(hipMemcpyAsync(s.h_status, s.d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, s.s));
   XD_HIP(hipEventRecord(s.done, s.s));
@@ -970,7 +1151,7 @@ RMSF_EXPORT int rmsf_xtcdec_decode(rmsf_xtcdec *d, int64_t f0, int64_t n, int64_
 
 RMSF_EXPORT int rmsf_xtcdec_decode_into(rmsf_xtcdec *d, int64_t f0, int64_t n, int64_t step, float *d_out,
                                         int64_t out_stride, void *consumer_stream, int *slot) {
-  if (!d || !slot || !d_out || out_stride < 3 * d->n_atoms || n < 1 || n > d->batch || step < 1 || f0 < 0 ||
+  if (!d || !slot || !d_out || out_stride < 3 * d->n_rows || n < 1 || n > d->batch || step < 1 || f0 < 0 ||
       f0 + (n - 1) * step >= (int64_t)d->x->offset.size())
     return fail(RMSF_EINVAL, "rmsf_xtcdec_decode_into: bad arguments");
   return xtcdec_decode(d, f0, n, step, d_out, out_stride, consumer_stream, slot, nullptr);

@@ -556,11 +556,21 @@ class HostSource:
 
 
 class XtcDecoder:
-    """ctypes handle on the pinned-slot GPU XTC decoder (rmsf_xtcdec_*)."""
+    """ctypes handle on the pinned-slot GPU XTC decoder (rmsf_xtcdec_*).
+    ``sel`` (atom indices, any order, each once): only those atoms are
+    decoded, as compact frames of ``n_rows = len(sel)`` rows in that order
+    (rmsf_xtcdec_create_sel); default: every atom."""
 
-    def __init__(self, xtc, batch_frames: int, n_slots: int = 3, n_threads: int = 8):
+    def __init__(self, xtc, batch_frames: int, n_slots: int = 3, n_threads: int = 8, sel=None):
         self._h = ctypes.c_void_p()
-        call("rmsf_xtcdec_create", xtc.handle, batch_frames, n_slots, n_threads, ctypes.byref(self._h))
+        if sel is None:
+            call("rmsf_xtcdec_create", xtc.handle, batch_frames, n_slots, n_threads, ctypes.byref(self._h))
+            self.n_rows = xtc.n_atoms
+        else:
+            s = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1)
+            call("rmsf_xtcdec_create_sel", xtc.handle, batch_frames, n_slots, n_threads, s.ctypes.data, s.size,
+                 ctypes.byref(self._h))
+            self.n_rows = int(s.size)
         self.batch_frames, self.n_slots = batch_frames, n_slots
 
     def decode(self, first: int, n: int, step: int, stream: int) -> tuple[int, int]:
@@ -611,11 +621,21 @@ class XtcSource:
     ``cache=True`` (GPU decode): decoded frames stay resident in HBM, so a
     second sweep over the trajectory -- RMSF.py re-reads every frame for its
     second loop (RMSF.py:124) -- reads them from HBM instead of decoding
-    again; ignored (with no error) when the trajectory would take more than
-    half of the free device memory."""
+    again; ignored (with no error) when the cached frames would take more
+    than half of the free device memory.
+
+    ``decode_select`` (GPU decode): the decoder writes the selected atoms
+    only (rmsf_xtcdec_create_sel) -- RMSF.py keeps 214 CA atoms of 47,681
+    (RMSF.py:77,126), 1/220 of what a whole-frame decode writes to HBM.
+    Slots, batches and the cache are then compact [.., n_sel, 3] rows in the
+    selection's order, the same batches as ``decode="host"`` stages.  ``None``
+    (default): on when the selection is a proper subset of the atoms with no
+    index listed twice.  ``False``: whole frames, the selection gathered by
+    the kernels.  ``True``: required (ValueError for a selection with a
+    duplicate index, which has no single output row)."""
 
     def __init__(self, path, sel=None, batch_frames: int | None = None, n_slots: int = 3, n_threads: int = 16,
-                 decode: str = "gpu", cache: bool = False):
+                 decode: str = "gpu", cache: bool = False, decode_select: bool | None = None):
         from .xtc import XTCFile
 
         if decode not in ("gpu", "host"):
@@ -627,21 +647,36 @@ class XtcSource:
             raise IndexError("selection index out of range")
         self.n_sel = self.n_atoms if sel_arr is None else len(sel_arr)
         self.decode_on = decode
+        unique = sel_arr is not None and sel_arr.size > 0 and np.unique(sel_arr).size == sel_arr.size
+        if decode_select is None:
+            decode_select = decode == "gpu" and unique and self.n_sel < self.n_atoms
+        elif decode_select:
+            if decode != "gpu":
+                raise ValueError("decode_select applies to decode='gpu'")
+            if sel_arr is None or sel_arr.size == 0:
+                raise ValueError("decode_select=True needs a selection")
+            if not unique:
+                raise ValueError("decode_select=True: the selection lists an atom twice, which has no single "
+                                 "output row; pass decode_select=False (the kernels gather the selection)")
+        self.decode_select = bool(decode_select)
+        # rows per decoded frame in the slots and the cache
+        self._rows = self.n_sel if self.decode_select else self.n_atoms
         if decode == "gpu":
-            if batch_frames is None:  # ~2 GB of decoded frames per slot
+            if batch_frames is None:  # the compressed records of ~2 GB of whole frames per pinned slot
                 batch_frames = max(1, min(4096, (2 << 30) // max(1, 12 * self.n_atoms)))
-            self.decoder = XtcDecoder(self.xtc, batch_frames, n_slots, n_threads)
+            self.decoder = XtcDecoder(self.xtc, batch_frames, n_slots, n_threads,
+                                      sel=sel_arr if self.decode_select else None)
             self.cache = None
             self._gather = None  # scratch for scattered frame lists served from the cache
             if cache:
-                need = 12 * self.n_atoms * self.n_traj
+                need = 12 * self._rows * self.n_traj
                 free, _ = torch.cuda.mem_get_info()
                 if need <= free // 2:
-                    self.cache = torch.empty((self.n_traj, self.n_atoms, 3), dtype=torch.float32,
+                    self.cache = torch.empty((self.n_traj, self._rows, 3), dtype=torch.float32,
                                              device=torch.cuda.current_device())
                     self._cached = np.zeros(self.n_traj, dtype=bool)
-            self.sel_dev = None
-            if sel_arr is not None and not np.array_equal(sel_arr, np.arange(self.n_sel)):
+            self.sel_dev = None  # selected decode: compact batches, nothing to gather
+            if not self.decode_select and sel_arr is not None and not np.array_equal(sel_arr, np.arange(self.n_sel)):
                 self.sel_dev = torch.as_tensor(sel_arr.astype(np.int32)).to(torch.cuda.current_device())
         else:
             if batch_frames is None:
@@ -659,7 +694,7 @@ class XtcSource:
 
     def _stage(self, first: int, step: int, n: int, stream: int) -> Batch:
         if self.decode_on == "gpu" and self.cache is not None:
-            fs = 3 * self.n_atoms
+            fs = 3 * self._rows
             ptr = self.cache.data_ptr() + 4 * fs * first
             rows = first + step * np.arange(n)
             release = None
@@ -670,7 +705,7 @@ class XtcSource:
             return Batch(ptr, fs * step, n, self.sel_dev, release)
         if self.decode_on == "gpu":
             slot, ptr = self.decoder.decode(first, n, step, stream)
-            return Batch(ptr, 3 * self.n_atoms, n, self.sel_dev, lambda: self.decoder.release(slot, stream))
+            return Batch(ptr, 3 * self._rows, n, self.sel_dev, lambda: self.decoder.release(slot, stream))
         slot, dptr = ctypes.c_int(), ctypes.c_void_p()
         call("rmsf_stager_stage_xtc", self.stager._h, self.xtc.handle, first, n, step, stream, ctypes.byref(slot),
              ctypes.byref(dptr))
@@ -706,7 +741,7 @@ class XtcSource:
         """Frames ``part`` of an explicit frame list (scattered records):
         decoded as ONE batch (rmsf_xtcdec_decode_list) instead of one decode
         per run; with the HBM cache their rows are copied in."""
-        fs = 3 * self.n_atoms
+        fs = 3 * self._rows
         slot, ptr = self.decoder.decode_list(part, stream)
         if self.cache is not None:
             w = 4 * fs
@@ -723,7 +758,7 @@ class XtcSource:
         before gathering again)."""
         if self._gather is None or self._gather.buf.shape[0] < len(part):
             self._gather = _Gather(self.n_sel, self.batch_frames, self.cache.device)
-        return self._gather(self.cache.data_ptr(), 3 * self.n_atoms, part, self.sel_dev, stream)
+        return self._gather(self.cache.data_ptr(), 3 * self._rows, part, self.sel_dev, stream)
 
     def batches(self, frames: FrameList, b0: int, b1: int, max_frames: int, stream: int) -> Iterator[Batch]:
         ahead = self.decoder.n_slots - 1 if self.decode_on == "gpu" else 0
