@@ -497,6 +497,42 @@ int rmsf_accumulate_sequential(const float *d_xyz, int64_t frame_stride,
 int rmsf_finalize(const double *d_m2, int64_t n_sel, int64_t n_frames,
                   double *d_rmsf, void *stream);
 
+/* ---- positional covariance (the preamble of MDAnalysis.analysis.pca.PCA) --
+ * The co-moment matrix of the selected coordinates, of which RMSF.py:146's
+ * RMSF is the diagonal, on the f64 matrix cores (v_mfma_f64_16x16x4_f64;
+ * csrc/covariance.hip).  Coordinate index i = 3 a + c over the selection's
+ * order (atom d_sel[a], or a when d_sel is NULL; rows only).
+ * rmsf_covariance_accumulate, for every frame f of the batch:
+ *   p = the atom's three floats -- through the transform of RMSF.py:99-101 /
+ *       133-135 with the frame's record d_xform[f] and ref_com =
+ *       d_refinfo[0..2] when both are given (the same device function the
+ *       accumulate runs: the Welford sweep's coordinates bit for bit), the
+ *       raw floats when both are NULL;
+ *   d = f64(p) - d_shift (f64 [3 n_sel], something near the data);
+ *   d_cov[i * ld + j] += sum_f d_i d_j  for every 48 x 48 block that holds an
+ *       element with j >= i (the strict lower blocks are not touched);
+ *   d_t1[i] += sum_f d_i.
+ * The caller zeroes d_cov (ld >= 3 n_sel doubles a row) and d_t1 before the
+ * first batch.  Work is cut into (tile pair, frame range) workgroups; with
+ * more than one frame range the partials go to d_work
+ * (rmsf_covariance_workspace_bytes() bytes, 0 when none is needed and d_work
+ * may be NULL) and are summed in frame order by a second launch: no
+ * floating-point atomics, the same bits for the same inputs and batching.
+ * rmsf_covariance_finish, after the last batch (and after d_cov and d_t1 were
+ * summed over the ranks), over n_frames frames in all:
+ *   d_cov = d_cov - d_t1 d_t1^T / n_frames, the centred co-moment, read from
+ *   the upper triangle and written to both, exactly symmetric.
+ * covariance = d_cov / n_frames (numpy.cov: / (n_frames - 1)).              */
+size_t rmsf_covariance_workspace_bytes(int64_t n_sel, int64_t n_frames);
+int rmsf_covariance_accumulate(const float *d_xyz, int64_t frame_stride,
+                               int64_t n_frames, int64_t n_sel,
+                               const int32_t *d_sel, const double *d_xform,
+                               const double *d_refinfo, const double *d_shift,
+                               double *d_cov, int64_t ld, double *d_t1,
+                               void *d_work, size_t work_bytes, void *stream);
+int rmsf_covariance_finish(double *d_cov, int64_t ld, const double *d_t1,
+                           int64_t n_coord, int64_t n_frames, void *stream);
+
 /* ---- qcprot.CalcRMSDRotationalMatrix (RMSF.py:48) --------------------------
  * Batched QCP on device: A[n][9], E0[n], atom counts N[n] -> rot[n][9],
  * rmsd[n].  Exposed for the upstream known-answer test.                      */

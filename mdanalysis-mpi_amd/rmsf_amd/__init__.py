@@ -6,16 +6,21 @@ Public surface (mirrors the reference's names):
   * ``second_order_moments`` / ``get_rotation_matrix`` / ``CalcRMSDRotationalMatrix``
     (device-backed versions of RMSF.py:36-51 and MDAnalysis.lib.qcprot)
   * ``blocks`` -- the RMSF.py:65-69 frame decomposition
+  * ``PCA`` / ``pca_from_comoment`` -- the modes of the positional covariance
+    (``RMSF(..., covariance=True)``), named as MDAnalysis.analysis.pca.PCA names them
 """
 from ._lib import RmsfEmptyError, RmsfError, load as load_library
 from .parallel import blocks
 from .qcprot import CalcRMSDRotationalMatrix, get_rotation_matrix
 from .moments import second_order_moments
 from .rms import RMSF, Results
+from .pca import PCA, pca_from_comoment
 
 __all__ = [
     "RMSF",
     "Results",
+    "PCA",
+    "pca_from_comoment",
     "blocks",
     "second_order_moments",
     "get_rotation_matrix",

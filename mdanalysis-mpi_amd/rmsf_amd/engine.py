@@ -381,6 +381,36 @@ class Engine:
         """RMSF.py:146: sqrt(M2.sum(axis=1)/n)."""
         call("rmsf_finalize", m2.data_ptr(), n_sel, n_frames, out.data_ptr(), self.stream)
 
+    # -- positional covariance (csrc/covariance.hip) --------------------------
+    def covariance_workspace_bytes(self, n_sel: int, n_frames: int) -> int:
+        return int(self.lib.rmsf_covariance_workspace_bytes(n_sel, n_frames))
+
+    def covariance_accumulate(self, xyz_ptr: int, fstride: int, n_frames: int, n_sel: int, sel, xform, refinfo,
+                              shift: torch.Tensor, cov: torch.Tensor, t1: torch.Tensor,
+                              work: torch.Tensor | None = None) -> None:
+        """cov[i, j] += sum_f d_i d_j (blocks holding j >= i), t1[i] += sum_f d_i
+        over the batch, d = f64(p) - shift with p the selected rows -- through
+        the transform of RMSF.py:99-101 / 133-135 when ``xform`` and
+        ``refinfo`` are given -- on the f64 matrix cores
+        (rmsf_covariance_accumulate).  ``work``: f64 scratch of at least
+        covariance_workspace_bytes(n_sel, n_frames) bytes (None when 0)."""
+        n = 3 * n_sel
+        if (cov.dtype != F64 or t1.dtype != F64 or shift.dtype != F64 or cov.dim() != 2 or cov.stride(1) != 1
+                or cov.shape[0] < n or cov.shape[1] < n or t1.numel() < n or shift.numel() < n):
+            raise ValueError("covariance_accumulate: buffer sizes")
+        call("rmsf_covariance_accumulate", xyz_ptr, fstride, n_frames, n_sel, _ptr(sel), _ptr(xform), _ptr(refinfo),
+             shift.data_ptr(), cov.data_ptr(), cov.stride(0), t1.data_ptr(), _ptr(work),
+             0 if work is None else work.numel() * work.element_size(), self.stream)
+
+    def covariance_finish(self, cov: torch.Tensor, t1: torch.Tensor, n_coord: int, n_frames: int) -> None:
+        """cov = cov - t1 t1^T / n_frames, the centred co-moment, mirrored
+        from the upper triangle to the full symmetric matrix
+        (rmsf_covariance_finish)."""
+        if cov.dim() != 2 or cov.stride(1) != 1 or cov.shape[0] < n_coord or cov.shape[1] < n_coord \
+                or t1.numel() < n_coord:
+            raise ValueError("covariance_finish: buffer sizes")
+        call("rmsf_covariance_finish", cov.data_ptr(), cov.stride(0), t1.data_ptr(), n_coord, n_frames, self.stream)
+
     def qcp_batch(self, A: torch.Tensor, E0: torch.Tensor, N: torch.Tensor):
         n = A.shape[0]
         rot = self.empty(n, 9)

@@ -181,6 +181,107 @@ class Accumulator:
         return self.parts1[0]
 
 
+class CovarianceAccumulator:
+    """Running co-moment sums of the last sweep's coordinates, on device:
+    ``cov`` [3n, 3n] += sum_f d d^T (the blocks of the upper triangle) and
+    ``t1`` [3n] += sum_f d, d = x - ``shift`` (f64 [3n], something every rank
+    holds near the data, as the cross-rank merge's shift), fed the batches
+    ``Accumulator.add`` gets (rmsf_covariance_accumulate: the f64 MFMA
+    kernel).  ``finish`` sums the ranks' and centres: M = C - T1 T1^T / N."""
+
+    def __init__(self, eng: Engine, n_sel: int, max_batch: int, shift: torch.Tensor,
+                 timer: KernelTimer | None = None):
+        self.eng, self.n_sel, self.timer = eng, n_sel, timer
+        self.n_coord = n = 3 * n_sel
+        check_covariance_memory(eng, n_sel)
+        if shift.dtype != torch.float64 or shift.numel() != n:
+            raise ValueError("the covariance shift is f64 [3 n_sel]")
+        self.shift = shift.reshape(-1)
+        self.cov = eng.zeros(n, n)
+        self.t1 = eng.zeros(n)
+        self.work = None
+        self._size(max_batch)
+
+    def _size(self, n_frames: int) -> None:
+        need = self.eng.covariance_workspace_bytes(self.n_sel, n_frames)
+        if need and (self.work is None or need > self.work.numel() * 8):  # not monotone in the batch size
+            self.work = self.eng.empty((need + 7) // 8)
+
+    def add(self, b: Batch, xform: torch.Tensor | None = None, refinfo: torch.Tensor | None = None) -> None:
+        if b.pstride:
+            raise NotImplementedError(_COV_PLANES)
+        self._size(b.n_frames)
+        with _span(self.timer, "covariance", b.n_frames * self.n_sel):
+            self.eng.covariance_accumulate(b.ptr, b.fstride, b.n_frames, self.n_sel, b.sel, xform,
+                                           refinfo if xform is not None else None, self.shift, self.cov, self.t1,
+                                           self.work)
+
+    def finish(self, n_total: int, root: int | None = None) -> torch.Tensor | None:
+        """The centred co-moment [3n, 3n] over all ranks' frames (None on the
+        non-root ranks of a reduce to ``root``)."""
+        rank, size = parallel.world()
+        if size > 1:
+            for t in (self.cov, self.t1):
+                if root is None:
+                    parallel.allreduce_sum_(t)
+                else:
+                    torch.distributed.reduce(t, dst=root, op=torch.distributed.ReduceOp.SUM)
+            if root is not None and rank != root:
+                return None
+        with _span(self.timer, "covariance_finish"):
+            self.eng.covariance_finish(self.cov, self.t1, self.n_coord, n_total)
+        return self.cov
+
+
+_COV_PLANES = ('covariance=True reads (frame, atom, xyz) rows; coordinate planes read in place are not supported -- '
+               'pass the trajectory with layout="fac"')
+
+
+def check_covariance_args(source, n_splits=None, merge_scatter: bool = False, merge_slabs=None) -> None:
+    """What ``covariance=True`` refuses, before any launch: the split grid,
+    the scatter merge and atom slabs (their merges slice the statistics by
+    atom; the matrix couples all atoms), and HBM-resident coordinate planes."""
+    if n_splits or merge_scatter or merge_slabs not in (None, 0, 1):
+        raise ValueError("covariance=True runs with the default merge only: no n_splits, merge_scatter or "
+                         "merge_slabs > 1")
+    if isinstance(source, DeviceSource) and source.layout == "soa":
+        raise NotImplementedError(_COV_PLANES)
+
+
+def check_covariance_memory(eng: Engine, n_sel: int) -> None:
+    """MemoryError if the [3n, 3n] f64 matrix is over half the free HBM."""
+    n = 3 * n_sel
+    need = 8 * n * n
+    free = torch.cuda.mem_get_info(eng.device)[0]
+    if need > free // 2:
+        raise MemoryError(f"covariance=True: the [{n}, {n}] f64 matrix needs {need} bytes, over half of the "
+                          f"{free} bytes of free HBM")
+
+
+def _covariance_shift(eng: Engine, source, frames: FrameList, align, average, ref, info, shift=None,
+                      shift_work=None) -> torch.Tensor:
+    """The f64 [3 n_sel] shift of the co-moment sums: the average
+    (align="average"), ref + ref_com (align="frame0"), or the selected rows of
+    the first frame of the list (``shift``/``shift_work``: already on its way
+    from its owner, _frame_shift)."""
+    if align == "average":
+        return average.reshape(-1)
+    if align == "frame0":
+        return (ref + info[:3]).reshape(-1)
+    if shift is None:
+        rank, size = parallel.world()
+        if size > 1:
+            shift, shift_work = _frame_shift(eng, source, frames, len(frames), size, rank)
+        else:
+            shift = torch.empty(3 * source.n_sel, dtype=torch.float32, device=eng.device)
+            b = source.reference(frames[0], eng.stream)
+            eng.gather_frames(b.ptr, b.fstride, eng.zero_index(), 1, source.n_sel, b.sel, shift)
+            b.done()
+    if shift_work is not None:
+        shift_work.wait()
+    return shift.double()
+
+
 class Superposer:
     """Per-frame COM + inner product + QCP for one batch (rmsf_superpose)."""
 
@@ -274,6 +375,14 @@ class PipelineResult:
     transforms: torch.Tensor | None = None
     transforms_sweep1: torch.Tensor | None = None
     extras: dict = field(default_factory=dict)
+    # covariance=True: the centred co-moment sum_f (x - mean)(x - mean)^T of
+    # the last sweep's coordinates, f64 [3 n_sel, 3 n_sel], index 3 a + c
+    comoment: torch.Tensor | None = None
+
+    @property
+    def covariance(self) -> torch.Tensor | None:
+        """comoment / n_frames (its diagonal, summed per atom, is rmsf**2)."""
+        return None if self.comoment is None else self.comoment / self.n_frames
 
 
 # Below this many frames an aligned run takes the exact path by default.  One
@@ -450,7 +559,7 @@ def run_pipeline(eng: Engine, source, frames: FrameList, *, align=None, masses=N
                  timer: KernelTimer | None = None, collect_transforms: bool = False,
                  merge_slabs: int | None = None, merge_root: int | None = None,
                  merge_scatter: bool = False, exact: bool | None = None, merge_order: str = "mpi4py",
-                 compact: bool | None = None) -> PipelineResult:
+                 compact: bool | None = None, covariance: bool = False) -> PipelineResult:
     """``merge_slabs`` (N > 1, no alignment, HBM-resident block in one batch,
     flat chunk-aligned plan): cut the final sweep into that many atom slabs
     so each slab's cross-rank all-reduce overlaps the next slab's stream;
@@ -481,7 +590,14 @@ def run_pipeline(eng: Engine, source, frames: FrameList, *, align=None, masses=N
     rows): the first pass writes the selected rows out dense and the later
     passes read them (_Compactor); None = below COMPACT_MAX_DENSITY (two
     sweeps) or COMPACT_MAX_DENSITY_ONE_SWEEP (one) selected atoms per frame
-    atom.  Same bits either way."""
+    atom.  Same bits either way.
+    ``covariance``: also form the positional co-moment matrix of the last
+    sweep's coordinates (``PipelineResult.comoment`` / ``.covariance``;
+    CovarianceAccumulator), summed over the ranks like the statistics (to
+    ``merge_root`` when set).  Off: not one extra launch or allocation."""
+    if covariance:
+        check_covariance_args(source, n_splits, merge_scatter, merge_slabs)
+        check_covariance_memory(eng, source.n_sel)
     if align not in ALIGN_MODES:
         raise ValueError(f"align must be one of {ALIGN_MODES}, got {align!r}")
     if exact is None:
@@ -494,7 +610,7 @@ def run_pipeline(eng: Engine, source, frames: FrameList, *, align=None, masses=N
             raise ValueError("collect_rmsd / collect_transforms need an aligned run")
         return _run_exact(eng, source, frames, max_batch, block, timer, merge_root, merge_order, align=align,
                           masses=masses, ref_frame=ref_frame, ref_owner=ref_owner, collect_rmsd=collect_rmsd,
-                          collect_transforms=collect_transforms)
+                          collect_transforms=collect_transforms, covariance=covariance)
     rank, size = parallel.world()
     n_total = len(frames)
     if n_total == 0:
@@ -547,7 +663,7 @@ def run_pipeline(eng: Engine, source, frames: FrameList, *, align=None, masses=N
     xf_first = eng.empty(n_local, RMSF_XFORM_DOUBLES) if (keep and align == "average") else None
     average = None
 
-    def sweep(acc: Accumulator, ref=None, info=None, xf_out=None, pack=None, slabs=None, fin=None):
+    def sweep(acc: Accumulator, ref=None, info=None, xf_out=None, pack=None, slabs=None, fin=None, cov=None):
         done, slabbed = 0, None
         if cmp is not None and cmp.resident and cmp.filled:   # a later sweep: the dense block, no gather
             batches = cmp.resident_batches(n_local, max_batch)
@@ -577,6 +693,8 @@ def run_pipeline(eng: Engine, source, frames: FrameList, *, align=None, masses=N
                                           root)
             if slabbed is None:
                 acc.add(b, xf, info, pack if last else None, fin if last else None)
+            if cov is not None:
+                cov.add(b, xf, info)
             done += b.n_frames
             src_b.done()
         if cmp is not None and cmp.resident:
@@ -616,13 +734,21 @@ def run_pipeline(eng: Engine, source, frames: FrameList, *, align=None, masses=N
     t = (torch.empty(2 * sc * size if scatter else 6 * n_sel, dtype=torch.float64, device=eng.device)
          if size > 1 else None)
     k_slabs = merge_slabs if merge_slabs is not None else (SLABS_AUTO if n_sel >= SLAB_MIN_ATOMS else 0)
-    slabs = k_slabs if (size > 1 and k_slabs > 1 and not aligned and not n_splits and not scatter) else None
+    slabs = k_slabs if (size > 1 and k_slabs > 1 and not aligned and not n_splits and not scatter
+                        and not covariance) else None
     slabbed = None
     # one rank, aligned: the last fold also finalises (RMSF.py:146)
     rmsf_fin = eng.empty(n_sel) if (size == 1 and aligned) else None
+    covacc = comoment = None
+    if covariance:
+        covacc = CovarianceAccumulator(eng, n_sel, max_batch,
+                                       _covariance_shift(eng, source, frames, align, average, ref, info, shift,
+                                                         shift_work), timer)
     if n_local:
         slabbed = sweep(acc, ref, info, xf_last, (shift, off3, t, shift_work, sc) if size > 1 else None, slabs,
-                        (rmsf_fin, n_total) if rmsf_fin is not None else None)
+                        (rmsf_fin, n_total) if rmsf_fin is not None else None, covacc)
+    if covacc is not None:
+        comoment = covacc.finish(n_total, root)
     if slabbed is not None:                                  # RMSF.py:141-143 + 146, slab by slab
         if root is not None and rank != root:
             with _span(timer, "merge"):                      # the exposed part: waits for the slabs' reduces
@@ -667,7 +793,7 @@ def run_pipeline(eng: Engine, source, frames: FrameList, *, align=None, masses=N
             return PipelineResult(rmsf=None, mean=None, m2=None, n_frames=n_total, n_local=n_local,
                                   block=(b0, b1), average=None if average is None else average.view(n_sel, 3),
                                   rmsd=rmsd, transforms=xf_last, transforms_sweep1=xf_first,
-                                  extras={"merge_root": root})
+                                  extras={"merge_root": root}, comoment=comoment)
     elif planes:
         mean, m2, rmsf = _rows_from_planes(eng, acc.result0, acc.result1, n_sel, n_total)
     else:
@@ -680,7 +806,7 @@ def run_pipeline(eng: Engine, source, frames: FrameList, *, align=None, masses=N
     return PipelineResult(rmsf=rmsf, mean=mean.view(n_sel, 3), m2=m2.view(n_sel, 3), n_frames=n_total,
                           n_local=n_local, block=(b0, b1),
                           average=None if average is None else average.view(n_sel, 3), rmsd=rmsd,
-                          transforms=xf_last, transforms_sweep1=xf_first)
+                          transforms=xf_last, transforms_sweep1=xf_first, comoment=comoment)
 
 
 EXACT_OVERLAP_MIN_ATOMS = 16384
@@ -689,7 +815,7 @@ EXACT_OVERLAP_MIN_ATOMS = 16384
 def _run_exact(eng: Engine, source, frames: FrameList, max_batch, block, timer, merge_root,
                merge_order: str = "mpi4py", *, align=None, masses=None, ref_frame: int = 0,
                ref_owner: int | None = None, collect_rmsd: bool = False,
-               collect_transforms: bool = False) -> PipelineResult:
+               collect_transforms: bool = False, covariance: bool = False) -> PipelineResult:
     """run_pipeline(exact=True): RMSF.py bit for bit (see there)."""
     rank, size = parallel.world()
     n_total = len(frames)
@@ -753,7 +879,7 @@ def _run_exact(eng: Engine, source, frames: FrameList, max_batch, block, timer, 
                 t.record_stream(main)
         return out, (centred, done)
 
-    def sweep(mode, acc0, acc1, ref=None, info=None, xf_out=None, pending=None):
+    def sweep(mode, acc0, acc1, ref=None, info=None, xf_out=None, pending=None, cov=None):
         work, k = None, 0
         for b in source.batches(frames, b0, b1, max_batch, eng.stream):  # rows: (frame, atom, xyz)
             if b.pstride:
@@ -782,6 +908,8 @@ def _run_exact(eng: Engine, source, frames: FrameList, max_batch, block, timer, 
                                               acc1, work)
                 else:
                     work = eng.welford_sequential(b.ptr, b.fstride, b.n_frames, n_sel, b.sel, k, acc0, acc1, work)
+            if cov is not None:
+                cov.add(b, x, info)
             k += b.n_frames
             b.done()
 
@@ -811,10 +939,18 @@ def _run_exact(eng: Engine, source, frames: FrameList, max_batch, block, timer, 
         else:
             average, ref, info = ref_avg_setup()
     mean, ss = eng.zeros(3 * n_sel), eng.zeros(3 * n_sel)       # RMSF.py:120-121
+    covacc = comoment = None
+    if covariance:
+        if pending is not None:   # the shift is made from the side stream's reference
+            main.wait_event(pending[1])
+        covacc = CovarianceAccumulator(eng, n_sel, max_batch,
+                                       _covariance_shift(eng, source, frames, align, average, ref, info), timer)
     if n_local:
-        sweep(RMSF_MODE_WELFORD, mean, ss, ref, info, xf_last, pending)  # RMSF.py:123-138
+        sweep(RMSF_MODE_WELFORD, mean, ss, ref, info, xf_last, pending, covacc)  # RMSF.py:123-138
     elif pending is not None:
         main.wait_event(pending[1])
+    if covacc is not None:
+        comoment = covacc.finish(n_total, root)
     if size > 1:                                                # RMSF.py:141-143, comm.reduce's order
         with _span(timer, "merge"):
             mean, ss = parallel.global_chan_exact(eng, mean, ss, [e - s for s, e in blocks], root, merge_order)
@@ -826,7 +962,7 @@ def _run_exact(eng: Engine, source, frames: FrameList, max_batch, block, timer, 
                           m2=None if ss is None else ss.view(n_sel, 3), n_frames=n_total, n_local=n_local,
                           block=(b0, b1), average=None if average is None else average.view(n_sel, 3), rmsd=rmsd,
                           transforms=xf_last, transforms_sweep1=xf_first,
-                          extras={"exact": True, "merge_root": root, "merge_order": merge_order})
+                          extras={"exact": True, "merge_root": root, "merge_order": merge_order}, comoment=comoment)
 
 
 class UploadedMasses:

@@ -28,6 +28,10 @@ as ``AnalysisBase.run``; taken in ascending order, so ``results.rmsd`` with
 sweep: the rotation of RMSF.py:48-51 row-major in 0..8, the mobile centre of
 mass of RMSF.py:94 in 9..11, the QCP rmsd in 12 -- and, for
 ``align="average"``, ``results.transforms_sweep1`` for RMSF.py's first sweep.
+
+``covariance=True`` adds the off-diagonal part of what the RMSF is the
+diagonal of: ``results.comoment`` and ``results.covariance`` (see ``RMSF``);
+``rmsf_amd.PCA`` takes its eigenvectors.
 """
 from __future__ import annotations
 
@@ -126,6 +130,20 @@ class RMSF:
         is upstream and absent here: its tree is restated from its published
         source, not verified, so from 4 ranks the bit-for-bit claim rests on
         that restatement (parity unpinned there).
+    covariance : bool
+        Also return the positional covariance of the coordinates the
+        statistics are taken over (the aligned ones of the last sweep):
+        ``results.comoment`` = sum_f (x_f - mean)(x_f - mean)^T and
+        ``results.covariance`` = comoment / n_frames, host f64 [3n, 3n],
+        coordinate order 3 a + c over the selection's order.  Formed on the
+        f64 matrix cores from the very coordinates the Welford sweep reads, so
+        ``covariance.diagonal().reshape(n, 3).sum(1) == rmsf**2`` up to
+        rounding.  Under ``torch.distributed`` the ranks' sums are all-reduced
+        (reduced to ``merge_root`` when set; None elsewhere).  Not with
+        ``n_splits``, ``merge_scatter``, HBM-resident ``layout="soa"`` planes
+        (ValueError / NotImplementedError), nor with ``gpus=`` or a list of
+        shards (NotImplementedError); a matrix over half the free HBM is a
+        MemoryError.
     gpus : int | list of int, optional
         Drive this many devices (or these device ids) from one process: each
         takes the RMSF.py:65-69 block of its index and the blocks merge over
@@ -140,7 +158,8 @@ class RMSF:
                  device=None, batch_frames: int | None = None, n_splits: int | None = None,
                  collect_rmsd: bool = False, verbose: bool = False, gpus=None,
                  collect_transforms: bool = False, layout: str = "fac", merge_root: int | None = None,
-                 merge_scatter: bool = False, exact: bool | None = None, merge_order: str = "mpi4py", **kwargs):
+                 merge_scatter: bool = False, exact: bool | None = None, merge_order: str = "mpi4py",
+                 covariance: bool = False, **kwargs):
         if layout not in ("fac", "soa"):
             raise ValueError(f"layout must be 'fac' or 'soa', got {layout!r}")
         if layout == "soa" and not (isinstance(atomgroup, np.ndarray) or isinstance(atomgroup, torch.Tensor)):
@@ -153,6 +172,7 @@ class RMSF:
         from ._lib import merge_order as _order
         _order(merge_order)
         self.merge_order = merge_order
+        self.covariance = bool(covariance)
         self._input = atomgroup
         self.select = select
         self.align = align
@@ -171,12 +191,17 @@ class RMSF:
     # MDAnalysis AnalysisBase compatible signature
     def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
         if self.gpus is not None or isinstance(self._input, (list, tuple)):
+            if self.covariance:
+                raise NotImplementedError("covariance=True is for one device per process (torch.distributed for "
+                                          "several); not with gpus= or a list of shards")
             if self.collect_transforms:
                 raise NotImplementedError("collect_transforms is for one device per process")
             if self.merge_scatter:
                 raise NotImplementedError("merge_scatter is for one process per GPU (torch.distributed); with "
                                           "gpus= the one process receives the merged result")
             return self._run_multi(start, stop, step, frames)  # several devices, or HBM shards per device
+        if self.covariance and (self.n_splits or self.merge_scatter):
+            raise ValueError("covariance=True runs with the default merge only: no n_splits or merge_scatter")
         eng = Engine(self.device)
         # torch's current device = the engine's, so the buffers sources and
         # caches allocate live on the device the kernels run on
@@ -191,7 +216,8 @@ class RMSF:
             res = run_pipeline(eng, src, fl, align=self.align, masses=masses, ref_frame=self.ref_frame,
                                max_batch=self.batch_frames, n_splits=self.n_splits, collect_rmsd=self.collect_rmsd,
                                collect_transforms=self.collect_transforms, merge_root=self.merge_root,
-                               merge_scatter=self.merge_scatter, exact=self.exact, merge_order=self.merge_order)
+                               merge_scatter=self.merge_scatter, exact=self.exact, merge_order=self.merge_order,
+                               **({"covariance": True} if self.covariance else {}))
             torch.cuda.current_stream(eng.device).synchronize()
             r = self.results
             host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731  (None: a non-root rank)
@@ -210,6 +236,9 @@ class RMSF:
                 r.transforms = res.transforms.cpu().numpy()
             if res.transforms_sweep1 is not None:
                 r.transforms_sweep1 = res.transforms_sweep1.cpu().numpy()
+            if self.covariance:
+                r.comoment = host(res.comoment)
+                r.covariance = None if r.comoment is None else r.comoment / res.n_frames
             if "atom_slice" in res.extras:  # merge_scatter: this rank's slice of the statistics
                 r.atom_slice = res.extras["atom_slice"]
                 r.slice_mean = res.extras["slice_mean"].cpu().numpy()

@@ -51,7 +51,12 @@ def main(argv=None) -> int:
     ap.add_argument("--merge-order", choices=["mpi4py", "rank"], default="mpi4py",
                     help="--exact, N>1: the order RMSF.py:143's comm.reduce applies second_order_moments in "
                          "(mpi4py: its default binomial tree; rank: rank order)")
+    ap.add_argument("--covariance", default=None, metavar="OUT.npy",
+                    help="also write the positional covariance of the (aligned) selected coordinates, f64 "
+                         "[3n, 3n] (co-moment / n_frames; not with --merge scatter), on rank 0")
     a = ap.parse_args(argv)
+    if a.covariance and a.merge == "scatter":
+        ap.error("--covariance needs --merge root or all")
     if a.exact and (a.align != "none" or a.merge == "scatter"):
         ap.error("--exact needs --align none and --merge root or all")
 
@@ -72,6 +77,8 @@ def main(argv=None) -> int:
     align = None if a.align == "none" else a.align
     rank, size = parallel.world()
     root = None if a.merge == "all" else 0
+    cov_kw = {"covariance": True} if a.covariance else {}
+    cov = None
     if a.synthetic:
         n_atoms, n_frames = a.synthetic
         eng = Engine()
@@ -81,8 +88,10 @@ def main(argv=None) -> int:
         shard = generate(eng, n_atoms, b0, max(b1 - b0, 1), seed=a.seed, motion=motion)[: b1 - b0]
         res = run_pipeline(eng, DeviceSource(shard, offset=b0, n_traj=n_frames), FrameList(n_frames),
                            align=align, ref_frame=a.ref_frame, merge_root=root, merge_scatter=a.merge == "scatter",
-                           exact=a.exact, merge_order=a.merge_order)
+                           exact=a.exact, merge_order=a.merge_order, **cov_kw)
         rmsf = None if res.rmsf is None else res.rmsf.cpu().numpy()   # None on the non-root ranks
+        if a.covariance and res.comoment is not None:
+            cov = res.covariance.cpu().numpy()
     else:
         if not (a.topology and a.trajectory):
             ap.error("--topology/--trajectory (MDAnalysis) or --synthetic is required")
@@ -93,9 +102,10 @@ def main(argv=None) -> int:
         if mda is not None:
             u = mda.Universe(a.topology, a.trajectory)
             ag = u.select_atoms(a.select)
-            rmsf = RMSF(ag, align=align, ref_frame=a.ref_frame, verbose=True, merge_root=root,
-                        merge_scatter=a.merge == "scatter", exact=a.exact,
-                        merge_order=a.merge_order).run().results.rmsf
+            results = RMSF(ag, align=align, ref_frame=a.ref_frame, verbose=True, merge_root=root,
+                           merge_scatter=a.merge == "scatter", exact=a.exact,
+                           merge_order=a.merge_order, **cov_kw).run().results
+            rmsf, cov = results.rmsf, (results.covariance if a.covariance else None)
         else:
             # native fallback: GRO or PSF topology + selection subset; XTC, DCD (or
             # multi-frame GRO) trajectory.  PSF masses (GRO: masses guessed from
@@ -111,13 +121,16 @@ def main(argv=None) -> int:
             masses = None if top.masses is None else top.masses[sel]
             traj = (a.trajectory if a.trajectory.lower().endswith((".xtc", ".dcd"))
                     else GroTopology(a.trajectory).frames)
-            rmsf = RMSF(traj, select=sel, align=align, masses=masses, ref_frame=a.ref_frame,
-                        verbose=True, merge_root=root, merge_scatter=a.merge == "scatter", exact=a.exact,
-                        merge_order=a.merge_order).run().results.rmsf
+            results = RMSF(traj, select=sel, align=align, masses=masses, ref_frame=a.ref_frame,
+                           verbose=True, merge_root=root, merge_scatter=a.merge == "scatter", exact=a.exact,
+                           merge_order=a.merge_order, **cov_kw).run().results
+            rmsf, cov = results.rmsf, (results.covariance if a.covariance else None)
     if rank == 0:
         print(f"RMSF over {len(rmsf)} atoms: mean {rmsf.mean():.6f} A, max {rmsf.max():.6f} A", flush=True)
         if a.out:
             np.save(a.out, rmsf)
+        if a.covariance:
+            np.save(a.covariance, cov)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
