@@ -533,6 +533,47 @@ int rmsf_covariance_accumulate(const float *d_xyz, int64_t frame_stride,
 int rmsf_covariance_finish(double *d_cov, int64_t ld, const double *d_t1,
                            int64_t n_coord, int64_t n_frames, void *stream);
 
+/* ---- all-pairs RMSD matrix (MDAnalysis.analysis.diffusionmap.DistanceMatrix)
+ * The n_frames x n_frames matrix of RMSDs between every pair of frames of a
+ * batch read at a constant frame_stride, on the f64 matrix cores
+ * (csrc/pairwise.hip): the covariance contraction turned on its side -- over
+ * the atoms, the frames' coordinates as rows.  For frames i, j
+ *   A_ij = sum_a w_a (x_i,a - c_i) (x_j,a - c_j)^T   (qcprot's inner product),
+ *   G_f  = sum_a w_a |x_f,a - c_f|^2,  E0 = (G_i + G_j) / 2,
+ * atom a = d_sel[a] (or a when d_sel is NULL; rows only), w = d_weights (NULL:
+ * unit weights), x = f64 of the atom's three floats.
+ * rmsf_pairwise_centres writes every frame's weighted centre c_f
+ * (d_centre[n_frames][3]) and G_f (d_g[n_frames]); per_frame = 0 gives every
+ * frame the centre of frame 0 -- a common shift for the metric without
+ * superposition, which does not depend on it (conditioning only).  Fixed
+ * summation order, no floating-point atomics.
+ * rmsf_pairwise_rmsd, from those, for every pair j > i:
+ *   superpose = 1: lambda = the largest root of the QCP quartic of A_ij by
+ *     Newton's iteration from E0 (the coefficients, start and stopping rule of
+ *     RMSF.py:48's qcprot, no rotation), d = sqrt(|2 (E0 - lambda)| / w_total)
+ *     -- the minimal RMSD of MDAnalysis.analysis.rms.rmsd(superposition=True);
+ *   superpose = 0: d = sqrt(|G_i + G_j - 2 tr A_ij| / w_total), the plain RMSD;
+ *   d <= cutoff is written as 0; d_out[i * ld + j] = d_out[j * ld + i] = d (one
+ *   value, stored twice: symmetric in its bits), the diagonal exactly 0.
+ * w_total = sum_a w_a (n_sel without weights), ld >= n_frames doubles a row.
+ * Work is cut into (pair of 16-frame tiles J >= I, atom range) workgroups;
+ * with more than one atom range (few frames, many atoms) the partial A_ij go
+ * to d_work (rmsf_pairwise_workspace_bytes() bytes, 0 when none is needed and
+ * d_work may be NULL) and are summed in atom order by a second launch.  The
+ * plan is a function of (n_frames, n_sel) alone: the same bits for the same
+ * inputs.                                                                    */
+int rmsf_pairwise_centres(const float *d_xyz, int64_t frame_stride,
+                          int64_t n_frames, int64_t n_sel, const int32_t *d_sel,
+                          const double *d_weights, int per_frame,
+                          double *d_centre, double *d_g, void *stream);
+size_t rmsf_pairwise_workspace_bytes(int64_t n_frames, int64_t n_sel);
+int rmsf_pairwise_rmsd(const float *d_xyz, int64_t frame_stride,
+                       int64_t n_frames, int64_t n_sel, const int32_t *d_sel,
+                       const double *d_weights, double w_total,
+                       const double *d_centre, const double *d_g, int superpose,
+                       double cutoff, double *d_out, int64_t ld, void *d_work,
+                       size_t work_bytes, void *stream);
+
 /* ---- qcprot.CalcRMSDRotationalMatrix (RMSF.py:48) --------------------------
  * Batched QCP on device: A[n][9], E0[n], atom counts N[n] -> rot[n][9],
  * rmsd[n].  Exposed for the upstream known-answer test.                      */

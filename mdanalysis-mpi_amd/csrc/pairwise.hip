@@ -1,0 +1,506 @@
+// pairwise.hip -- the all-pairs RMSD matrix of a trajectory's frames ("2D
+// RMSD", what MDAnalysis.analysis.diffusionmap.DistanceMatrix produces) on
+// the f64 matrix cores of gfx950 (MI355X, CDNA4), and the extern "C" launchers
+// declared in include/rmsf_hip.h.
+//
+// covariance.hip contracts over frames and keeps the atoms' coordinates as
+// rows; this is the same contraction turned on its side: over atoms, the
+// frames' coordinates as rows.  For frames i, j the 3 x 3 inner product of
+// qcprot,
+//
+//   A_ij = sum_a w_a (x_i,a - c_i) (x_j,a - c_j)^T,
+//
+// is one 3 x 3 block of the Gram matrix X W X^T; with E0 = (G_i + G_j) / 2,
+// G_f = sum_a w_a |x_f,a - c_f|^2, the largest root of the QCP quartic gives
+// the minimal RMSD without the rotation (Theobald 2005).
+//
+//   * k_pw_centres  one workgroup per frame: the weighted centre and G_f.
+//   * k_pw_tiles    one workgroup per (macro tile pair J >= I, atom range):
+//                   16 frames = 48 coordinates a side, rows coordinate-major
+//                   (row = 16 c + frame), 3 x 3 tiles of
+//                   v_mfma_f64_16x16x4_f64 per wave.  The deviations of 32
+//                   atoms are staged as f64 [atom][row] in LDS; each of the
+//                   4 waves contracts 8 of them.  With that row order one
+//                   lane's nine accumulators hold the nine entries of A_ij of
+//                   one frame pair per register.
+//   * k_pw_fold     the split-K partials, summed in atom-range order.
+//   * pair_epilogue lambda by Newton's iteration (or the trace, without
+//                   superposition), the cutoff, the store and its mirror.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "rmsf_hip.h"
+
+#define RMSF_EXPORT __attribute__((visibility("default")))
+
+extern "C" int rmsf_internal_set_error(int code, const char *msg);
+
+namespace {
+
+int fail(int code, const std::string &m) { return rmsf_internal_set_error(code, m.c_str()); }
+
+int after_launch(const char *what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(RMSF_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  return RMSF_OK;
+}
+
+inline hipStream_t S(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr int kTF = 16;                    // frames a side of a macro tile
+constexpr int kTC = 3 * kTF;               // rows a side: 3 MFMA tiles (x, y, z of the 16 frames)
+constexpr int kKA = 32;                    // atoms staged at a time (8 per wave: 2 MFMA k-steps)
+constexpr int kPitch = kTC + 2;            // doubles a staged atom: 50, so the 16 atom lanes of a frame
+                                           // store to 16 different LDS bank pairs
+constexpr int kAtomLanes = kBlock / kTF;   // lanes of a frame, along its atoms (a frame's row is contiguous)
+constexpr int kPasses = kKA / kAtomLanes;  // atoms a lane stages
+constexpr int kPairs = kTF * kTF;          // frame pairs of a tile pair: one per thread
+constexpr int kTile = 9 * kPairs;          // A_ij entries of a tile pair
+constexpr int64_t kTargetGroups = 512;     // 2 resident workgroups per CU on MI355X
+
+static_assert(kPairs == kBlock, "the epilogue gives every thread one frame pair");
+static_assert(kTile <= 2 * kKA * kPitch, "the waves' sum reuses the staging buffer");
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+// The work decomposition, a function of (n_frames, n_sel) alone, so the
+// workspace layout and the summation order are fixed by the sizes.
+struct PwPlan {
+  int64_t n_tiles;   // macro tiles a side
+  int64_t n_pairs;   // tile pairs J >= I
+  int64_t n_ks;      // atom ranges (split-K); 1 = the epilogue runs in k_pw_tiles
+  int64_t ks_atoms;  // atoms per range, a multiple of kKA
+};
+
+PwPlan pw_plan(int64_t n_frames, int64_t n_sel) {
+  PwPlan p;
+  p.n_tiles = (n_frames + kTF - 1) / kTF;
+  p.n_pairs = p.n_tiles * (p.n_tiles + 1) / 2;
+  const int64_t stages = std::max<int64_t>(1, (n_sel + kKA - 1) / kKA);
+  const int64_t ks = std::max<int64_t>(1, std::min<int64_t>(stages, kTargetGroups / p.n_pairs));
+  const int64_t per = (stages + ks - 1) / ks;
+  p.n_ks = (stages + per - 1) / per;
+  p.ks_atoms = per * kKA;
+  return p;
+}
+
+size_t pw_work_doubles(const PwPlan &p) {
+  if (p.n_ks <= 1) return 0;
+  return (size_t)p.n_ks * (size_t)p.n_pairs * kTile;
+}
+
+// pair index -> (I, J), J >= I, rows of the upper block triangle in order.
+// Row I starts at I n - I (I - 1) / 2; the root of that quadratic, then a
+// step either way for its rounding.
+__device__ __forceinline__ void pair_to_tiles(int64_t p, int64_t n_tiles, int64_t &I, int64_t &J) {
+  const double b = 2.0 * (double)n_tiles + 1.0;
+  int64_t i = (int64_t)((b - sqrt(b * b - 8.0 * (double)p)) * 0.5);
+  if (i < 0) i = 0;
+  if (i > n_tiles - 1) i = n_tiles - 1;
+  while (i > 0 && i * n_tiles - i * (i - 1) / 2 > p) --i;
+  while (i + 1 < n_tiles && (i + 1) * n_tiles - (i + 1) * i / 2 <= p) ++i;
+  I = i;
+  J = i + (p - (i * n_tiles - i * (i - 1) / 2));
+}
+
+// Sum of v over the workgroup in a fixed order (a halving tree over LDS);
+// every thread returns the total.
+__device__ __forceinline__ double block_sum(double v, double *__restrict__ sh) {
+  const int tid = threadIdx.x;
+  __syncthreads();  // sh may still be read from the call before
+  sh[tid] = v;
+  __syncthreads();
+  for (int s = kBlock / 2; s > 0; s >>= 1) {
+    if (tid < s) sh[tid] = sh[tid] + sh[tid + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// One workgroup per frame f: c = sum_a w_a x_a / sum_a w_a over the frame
+// (over frame 0 when !per_frame: a common shift), then G = sum_a w_a |x_f,a - c|^2.
+// Each thread adds its atoms in order, the threads are added by block_sum.
+template <bool GATHER>
+__global__ __launch_bounds__(kBlock) void k_pw_centres(const float *__restrict__ xyz, int64_t fstride, int64_t n_sel,
+                                                       const int32_t *__restrict__ sel,
+                                                       const double *__restrict__ weights, int per_frame,
+                                                       double *__restrict__ centre, double *__restrict__ g) {
+  __shared__ double sh[kBlock];
+  const int tid = threadIdx.x;
+  const int64_t f = blockIdx.x;
+  const float *__restrict__ src = xyz + (per_frame ? f : 0) * fstride;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, sw = 0.0;
+  for (int64_t a = tid; a < n_sel; a += kBlock) {
+    const float *__restrict__ q = src + 3 * (GATHER ? (int64_t)sel[a] : a);
+    const double w = weights ? weights[a] : 1.0;
+    s0 += w * (double)q[0], s1 += w * (double)q[1], s2 += w * (double)q[2], sw += w;
+  }
+  s0 = block_sum(s0, sh), s1 = block_sum(s1, sh), s2 = block_sum(s2, sh), sw = block_sum(sw, sh);
+  const double c0 = s0 / sw, c1 = s1 / sw, c2 = s2 / sw;
+  const float *__restrict__ own = xyz + f * fstride;
+  double gs = 0.0;
+  for (int64_t a = tid; a < n_sel; a += kBlock) {
+    const float *__restrict__ q = own + 3 * (GATHER ? (int64_t)sel[a] : a);
+    const double w = weights ? weights[a] : 1.0;
+    const double d0 = (double)q[0] - c0, d1 = (double)q[1] - c1, d2 = (double)q[2] - c2;
+    gs += w * (d0 * d0 + d1 * d1 + d2 * d2);
+  }
+  gs = block_sum(gs, sh);
+  if (tid == 0) {
+    centre[3 * f] = c0, centre[3 * f + 1] = c1, centre[3 * f + 2] = c2;
+    g[f] = gs;
+  }
+}
+
+// The largest root of the QCP quartic (Theobald, Acta Cryst A 61:478, 2005;
+// Liu et al., J Comput Chem 31:1561, 2010): the coefficients, the start
+// lambda = E0 and the stopping rule of qcp_solve (rmsf_device.h), without the
+// rotation.  A is the row-major 3 x 3 inner product.
+__device__ __forceinline__ double qcp_lambda(const double *A, double E0) {
+  const double Sxx = A[0], Sxy = A[1], Sxz = A[2];
+  const double Syx = A[3], Syy = A[4], Syz = A[5];
+  const double Szx = A[6], Szy = A[7], Szz = A[8];
+
+  const double Sxx2 = Sxx * Sxx, Syy2 = Syy * Syy, Szz2 = Szz * Szz;
+  const double Sxy2 = Sxy * Sxy, Syz2 = Syz * Syz, Sxz2 = Sxz * Sxz;
+  const double Syx2 = Syx * Syx, Szy2 = Szy * Szy, Szx2 = Szx * Szx;
+
+  const double SyzSzymSyySzz2 = 2.0 * (Syz * Szy - Syy * Szz);
+  const double Sxx2Syy2Szz2Syz2Szy2 = Syy2 + Szz2 - Sxx2 + Syz2 + Szy2;
+
+  const double C2 = -2.0 * (Sxx2 + Syy2 + Szz2 + Sxy2 + Syx2 + Sxz2 + Szx2 + Syz2 + Szy2);
+  const double C1 = 8.0 * (Sxx * Syz * Szy + Syy * Szx * Sxz + Szz * Sxy * Syx - Sxx * Syy * Szz -
+                           Syz * Szx * Sxy - Szy * Syx * Sxz);
+
+  const double SxzpSzx = Sxz + Szx, SyzpSzy = Syz + Szy, SxypSyx = Sxy + Syx;
+  const double SyzmSzy = Syz - Szy, SxzmSzx = Sxz - Szx, SxymSyx = Sxy - Syx;
+  const double SxxpSyy = Sxx + Syy, SxxmSyy = Sxx - Syy;
+  const double Sxy2Sxz2Syx2Szx2 = Sxy2 + Sxz2 - Syx2 - Szx2;
+
+  const double C0 =
+      Sxy2Sxz2Syx2Szx2 * Sxy2Sxz2Syx2Szx2 +
+      (Sxx2Syy2Szz2Syz2Szy2 + SyzSzymSyySzz2) * (Sxx2Syy2Szz2Syz2Szy2 - SyzSzymSyySzz2) +
+      (-(SxzpSzx) * (SyzmSzy) + (SxymSyx) * (SxxmSyy - Szz)) *
+          (-(SxzmSzx) * (SyzpSzy) + (SxymSyx) * (SxxmSyy + Szz)) +
+      (-(SxzpSzx) * (SyzpSzy) - (SxypSyx) * (SxxpSyy - Szz)) *
+          (-(SxzmSzx) * (SyzmSzy) - (SxypSyx) * (SxxpSyy + Szz)) +
+      (+(SxypSyx) * (SyzpSzy) + (SxzpSzx) * (SxxmSyy + Szz)) *
+          (-(SxymSyx) * (SyzmSzy) + (SxzpSzx) * (SxxpSyy + Szz)) +
+      (+(SxypSyx) * (SyzmSzy) + (SxzmSzx) * (SxxmSyy - Szz)) *
+          (-(SxymSyx) * (SyzpSzy) + (SxzmSzx) * (SxxpSyy - Szz));
+
+  double l = E0;
+  for (int i = 0; i < 50; ++i) {
+    const double old = l;
+    const double x2 = l * l;
+    const double b = (x2 + C2) * l;
+    const double a = b + C1;
+    const double delta = (a * l + C0) / (2.0 * x2 * l + b + a);
+    l -= delta;
+    if (fabs(l - old) < fabs(1e-11 * l)) break;
+  }
+  return l;
+}
+
+// Thread tid owns the frame pair (fi = tid >> 4 of tile I, fj = tid & 15 of
+// tile J) and its A_ij.  Pairs j > i are computed; each value goes to [i, j]
+// and, through LDS so that both stores run along rows, to [j, i]; the
+// diagonal is written as 0.  Called by every thread of the workgroup.
+__device__ __forceinline__ void pair_epilogue(const double *A, int64_t I, int64_t J, int64_t n_frames,
+                                              const double *__restrict__ g, int superpose, double w_total,
+                                              double cutoff, double *__restrict__ out, int64_t ld,
+                                              double (*__restrict__ sd)[kTF + 1]) {
+  const int tid = threadIdx.x;
+  const int fi = tid >> 4, fj = tid & 15;
+  const int64_t i = kTF * I + fi, j = kTF * J + fj;
+  const bool in = i < n_frames && j < n_frames;
+  double d = 0.0;
+  if (in && j > i) {
+    const double gi = g[i], gj = g[j];
+    const double E0 = (gi + gj) * 0.5;
+    if (superpose) {
+      // (two all-zero frames: the quartic is 0 / 0; their distance is 0)
+      const double l = E0 > 0.0 || E0 != E0 ? qcp_lambda(A, E0) : E0;
+      d = sqrt(fabs(2.0 * (E0 - l)) / w_total);
+    } else {
+      d = sqrt(fabs(gi + gj - 2.0 * (A[0] + A[4] + A[8])) / w_total);
+    }
+    if (d <= cutoff) d = 0.0;
+  }
+  if (I == J) {
+    // the tile is its own mirror image: the upper half fills both
+    if (fj > fi) sd[fi][fj] = d, sd[fj][fi] = d;
+    if (fj == fi) sd[fi][fi] = 0.0;
+    __syncthreads();
+    if (in) out[i * ld + j] = sd[fi][fj];
+  } else {
+    if (in) out[i * ld + j] = d;
+    sd[fi][fj] = d;
+    __syncthreads();
+    const int64_t jj = kTF * J + fi, ii = kTF * I + fj;  // row of tile J, column of tile I
+    if (jj < n_frames && ii < n_frames) out[jj * ld + ii] = sd[fj][fi];
+  }
+}
+
+// One workgroup: tile pair blockIdx.x, atoms [blockIdx.y ks_atoms, ...).
+// Staging: lane (tid & 15) walks the atoms of frame (tid >> 4) of the tile;
+// its three deviations f64(x) - c_f go to sm[op][atom k][16 c + frame]
+// (operand A times the atom's weight).  MFMA operands (16x16x4 f64): lane l
+// holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15], i.e. 16
+// consecutive doubles of staged atom k each; the result D has col = l & 15,
+// row = (l >> 4) + 4 reg -- so acc[ci][cj][reg] of lane l is entry (ci, cj)
+// of A_ij for frames i = (l >> 4) + 4 reg of tile I and j = l & 15 of tile J.
+template <bool GATHER, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict__ xyz, int64_t fstride,
+                                                     int64_t n_frames, int64_t n_sel,
+                                                     const int32_t *__restrict__ sel,
+                                                     const double *__restrict__ weights,
+                                                     const double *__restrict__ centre,
+                                                     const double *__restrict__ g, int superpose, double w_total,
+                                                     double cutoff, double *__restrict__ out, int64_t ld,
+                                                     double *__restrict__ work, int64_t n_tiles, int64_t n_pairs,
+                                                     int64_t ks_atoms, int direct) {
+  __shared__ double sm[2 * kKA * kPitch];  // A then B deviations; reused for the waves' sum
+  __shared__ double sd[kTF][kTF + 1];      // the tile's distances, for the mirrored store
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int ta = tid & (kAtomLanes - 1), tf = tid >> 4;
+  const int64_t pair = blockIdx.x, ks = blockIdx.y;
+  int64_t I, J;
+  pair_to_tiles(pair, n_tiles, I, J);
+  // a weighted diagonal tile still needs both operands: w d and d
+  const int n_ops = (I == J && !WEIGHTED) ? 1 : 2;
+
+  const int64_t a0 = ks * ks_atoms;
+  const int64_t a1 = a0 + ks_atoms < n_sel ? a0 + ks_atoms : n_sel;
+
+  // The lane's frame of each operand tile: its row, its centre, and whether
+  // it exists.  A lane past the last frame reads the last frame instead (and
+  // an atom past the range's end the range's last atom), so every load is
+  // unconditional and in bounds, and its deviation is zeroed after.
+  const float *p_op[2];
+  double cen[2][3];
+  bool live[2];
+#pragma unroll
+  for (int op = 0; op < 2; ++op) {
+    const int64_t f = kTF * (op ? J : I) + tf;
+    live[op] = f < n_frames;
+    const int64_t fc = live[op] ? f : n_frames - 1;
+    p_op[op] = xyz + fc * fstride;
+    cen[op][0] = centre[3 * fc], cen[op][1] = centre[3 * fc + 1], cen[op][2] = centre[3 * fc + 2];
+  }
+
+  f64x4 acc[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
+
+  const double *sA = sm;
+  const double *sB = n_ops == 1 ? sm : sm + kKA * kPitch;
+
+  // The next stage's floats are loaded into registers before the current
+  // stage's MFMAs, so the global-load latency runs under the matrix pipe;
+  // they become deviations in LDS after.
+  float raw[2][kPasses][3];
+  double wv[kPasses];
+  auto prefetch = [&](int64_t ab) {
+#pragma unroll
+    for (int pass = 0; pass < kPasses; ++pass) {
+      const int64_t a = ab + pass * kAtomLanes + ta;
+      const int64_t ac = a < a1 ? a : a1 - 1;
+      const int64_t row = 3 * (GATHER ? (int64_t)sel[ac] : ac);
+      if (WEIGHTED) wv[pass] = weights[ac];
+#pragma unroll
+      for (int op = 0; op < 2; ++op) {
+        if (op >= n_ops) break;
+        const float *__restrict__ q = p_op[op] + row;
+        raw[op][pass][0] = q[0], raw[op][pass][1] = q[1], raw[op][pass][2] = q[2];
+      }
+    }
+  };
+  prefetch(a0);
+
+  for (int64_t ab = a0; ab < a1; ab += kKA) {
+    // ---- stage kKA atoms of both operand tiles (zeros past either edge)
+#pragma unroll
+    for (int op = 0; op < 2; ++op) {
+      if (op >= n_ops) break;
+#pragma unroll
+      for (int pass = 0; pass < kPasses; ++pass) {
+        const int k = pass * kAtomLanes + ta;
+        const bool on = live[op] && ab + k < a1;
+        double d0 = on ? (double)raw[op][pass][0] - cen[op][0] : 0.0;
+        double d1 = on ? (double)raw[op][pass][1] - cen[op][1] : 0.0;
+        double d2 = on ? (double)raw[op][pass][2] - cen[op][2] : 0.0;
+        if (WEIGHTED && op == 0) d0 *= wv[pass], d1 *= wv[pass], d2 *= wv[pass];
+        double *__restrict__ o = sm + (op * kKA + k) * kPitch + tf;
+        o[0] = d0, o[kTF] = d1, o[2 * kTF] = d2;
+      }
+    }
+    __syncthreads();
+    // (after the barrier: its fence waits for every load in flight)
+    if (ab + kKA < a1) prefetch(ab + kKA);
+    // ---- contract: wave w takes atoms [8 w, 8 w + 8) of the staged tile
+#pragma unroll
+    for (int s = 0; s < kKA / (4 * kWaves); ++s) {
+      const int k = (kKA / kWaves) * wave + 4 * s + (lane >> 4);
+      const double *__restrict__ ra = sA + k * kPitch + (lane & 15);
+      const double *__restrict__ rb = sB + k * kPitch + (lane & 15);
+      const double x0 = ra[0], x1 = ra[kTF], x2 = ra[2 * kTF];
+      const double y0 = rb[0], y1 = rb[kTF], y2 = rb[2 * kTF];
+      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y1, acc[0][1], 0, 0, 0);
+      acc[0][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y2, acc[0][2], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y1, acc[1][1], 0, 0, 0);
+      acc[1][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y2, acc[1][2], 0, 0, 0);
+      acc[2][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, y0, acc[2][0], 0, 0, 0);
+      acc[2][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, y1, acc[2][1], 0, 0, 0);
+      acc[2][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, y2, acc[2][2], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+  // ---- the four waves' accumulators, summed in wave order through LDS
+  // (every wave maps lane -> element alike, so a lane only meets its own).
+  // Entry q = 3 ci + cj of the pair (fi = (lane >> 4) + 4 reg, fj = lane & 15)
+  // lands at sm[256 q + 16 fi + fj].
+  for (int w = 0; w < kWaves; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int e = kPairs * (3 * i + j) + kTF * ((lane >> 4) + 4 * r) + (lane & 15);
+            sm[e] = w == 0 ? acc[i][j][r] : sm[e] + acc[i][j][r];
+          }
+    }
+    __syncthreads();
+  }
+
+  if (direct) {
+    double A[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) A[q] = sm[kPairs * q + tid];
+    pair_epilogue(A, I, J, n_frames, g, superpose, w_total, cutoff, out, ld, sd);
+  } else {
+    double *__restrict__ w = work + ((int64_t)ks * n_pairs + pair) * kTile;
+    for (int e = tid; e < kTile; e += kBlock) w[e] = sm[e];
+  }
+}
+
+// The n_ks partials of every A_ij entry, summed in atom-range order, then
+// the epilogue.  One workgroup per tile pair.
+__global__ __launch_bounds__(kBlock) void k_pw_fold(const double *__restrict__ work, int64_t n_frames,
+                                                    int64_t n_tiles, int64_t n_pairs, int64_t n_ks,
+                                                    const double *__restrict__ g, int superpose, double w_total,
+                                                    double cutoff, double *__restrict__ out, int64_t ld) {
+  __shared__ double sd[kTF][kTF + 1];
+  const int tid = threadIdx.x;
+  const int64_t pair = blockIdx.x;
+  int64_t I, J;
+  pair_to_tiles(pair, n_tiles, I, J);
+  double A[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    const double *__restrict__ w = work + pair * kTile + kPairs * q + tid;
+    double s = 0.0;
+    for (int64_t k = 0; k < n_ks; ++k) s += w[k * n_pairs * kTile];
+    A[q] = s;
+  }
+  pair_epilogue(A, I, J, n_frames, g, superpose, w_total, cutoff, out, ld, sd);
+}
+
+// The LDS a kernel declares against the device's limit per workgroup, before
+// its first launch (a kernel over the limit would fail at launch with a less
+// helpful message).
+int lds_guard(const void *kernel, const char *name) {
+  hipFuncAttributes at;
+  hipError_t e = hipFuncGetAttributes(&at, kernel);
+  if (e != hipSuccess) return fail(RMSF_EHIP, std::string(name) + ": hipFuncGetAttributes: " + hipGetErrorString(e));
+  int dev = 0, limit = 0;
+  e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+  if (e != hipSuccess) return fail(RMSF_EHIP, std::string(name) + ": device LDS limit: " + hipGetErrorString(e));
+  if (at.sharedSizeBytes > (size_t)limit)
+    return fail(RMSF_EINVAL, std::string(name) + ": the kernel declares " + std::to_string(at.sharedSizeBytes) +
+                                 " bytes of LDS, the device allows " + std::to_string(limit) + " a workgroup");
+  return RMSF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+RMSF_EXPORT int rmsf_pairwise_centres(const float *d_xyz, int64_t fstride, int64_t n_frames, int64_t n_sel,
+                                      const int32_t *d_sel, const double *d_weights, int per_frame,
+                                      double *d_centre, double *d_g, void *stream) {
+  if (!d_xyz || !d_centre || !d_g || n_sel < 1 || n_frames < 0 || fstride < 0)
+    return fail(RMSF_EINVAL, "rmsf_pairwise_centres: bad arguments");
+  if (n_frames > INT32_MAX) return fail(RMSF_EINVAL, "rmsf_pairwise_centres: too many frames for one launch");
+  if (n_frames == 0) return RMSF_OK;
+  const dim3 grid((unsigned)n_frames), block(kBlock);
+  if (d_sel)
+    hipLaunchKernelGGL(k_pw_centres<true>, grid, block, 0, S(stream), d_xyz, fstride, n_sel, d_sel, d_weights,
+                       per_frame, d_centre, d_g);
+  else
+    hipLaunchKernelGGL(k_pw_centres<false>, grid, block, 0, S(stream), d_xyz, fstride, n_sel, d_sel, d_weights,
+                       per_frame, d_centre, d_g);
+  return after_launch("k_pw_centres");
+}
+
+RMSF_EXPORT size_t rmsf_pairwise_workspace_bytes(int64_t n_frames, int64_t n_sel) {
+  if (n_sel < 1 || n_frames < 1) return 0;
+  return pw_work_doubles(pw_plan(n_frames, n_sel)) * sizeof(double);
+}
+
+RMSF_EXPORT int rmsf_pairwise_rmsd(const float *d_xyz, int64_t fstride, int64_t n_frames, int64_t n_sel,
+                                   const int32_t *d_sel, const double *d_weights, double w_total,
+                                   const double *d_centre, const double *d_g, int superpose, double cutoff,
+                                   double *d_out, int64_t ld, void *d_work, size_t work_bytes, void *stream) {
+  if (!d_xyz || !d_centre || !d_g || !d_out || n_sel < 1 || n_frames < 0 || fstride < 0 || ld < n_frames ||
+      !(w_total > 0.0))
+    return fail(RMSF_EINVAL, "rmsf_pairwise_rmsd: bad arguments");
+  if (n_frames == 0) return RMSF_OK;
+  const PwPlan pl = pw_plan(n_frames, n_sel);
+  if (pl.n_pairs > INT32_MAX || pl.n_ks > 65535)
+    return fail(RMSF_EINVAL, "rmsf_pairwise_rmsd: too many frames for one launch");
+  const size_t need = pw_work_doubles(pl) * sizeof(double);
+  if (need && (!d_work || work_bytes < need)) return fail(RMSF_ENOMEM, "rmsf_pairwise_rmsd: workspace too small");
+  const int direct = pl.n_ks == 1;
+  double *work = static_cast<double *>(d_work);
+  const dim3 grid((unsigned)pl.n_pairs, (unsigned)pl.n_ks), block(kBlock);
+#define PW_LAUNCH(G_, W_)                                                                                          \
+  do {                                                                                                             \
+    if (int rc = lds_guard(reinterpret_cast<const void *>(k_pw_tiles<G_, W_>), "rmsf_pairwise_rmsd")) return rc;   \
+    hipLaunchKernelGGL((k_pw_tiles<G_, W_>), grid, block, 0, S(stream), d_xyz, fstride, n_frames, n_sel, d_sel,    \
+                       d_weights, d_centre, d_g, superpose, w_total, cutoff, d_out, ld, work, pl.n_tiles,          \
+                       pl.n_pairs, pl.ks_atoms, direct);                                                           \
+  } while (0)
+  const bool gt = d_sel != nullptr, wt = d_weights != nullptr;
+  if (gt && wt) PW_LAUNCH(true, true);
+  else if (gt) PW_LAUNCH(true, false);
+  else if (wt) PW_LAUNCH(false, true);
+  else PW_LAUNCH(false, false);
+#undef PW_LAUNCH
+  if (int rc = after_launch("k_pw_tiles")) return rc;
+  if (!direct) {
+    if (int rc = lds_guard(reinterpret_cast<const void *>(k_pw_fold), "rmsf_pairwise_rmsd")) return rc;
+    hipLaunchKernelGGL(k_pw_fold, dim3((unsigned)pl.n_pairs), block, 0, S(stream), work, n_frames, pl.n_tiles,
+                       pl.n_pairs, pl.n_ks, d_g, superpose, w_total, cutoff, d_out, ld);
+    if (int rc = after_launch("k_pw_fold")) return rc;
+  }
+  return RMSF_OK;
+}
+
+}  // extern "C"

@@ -8,6 +8,8 @@ Public surface (mirrors the reference's names):
   * ``blocks`` -- the RMSF.py:65-69 frame decomposition
   * ``PCA`` / ``pca_from_comoment`` -- the modes of the positional covariance
     (``RMSF(..., covariance=True)``), named as MDAnalysis.analysis.pca.PCA names them
+  * ``DistanceMatrix`` / ``DiffusionMap`` -- the all-pairs RMSD matrix of the frames and
+    its diffusion map, named as MDAnalysis.analysis.diffusionmap names them
 """
 from ._lib import RmsfEmptyError, RmsfError, load as load_library
 from .parallel import blocks
@@ -15,12 +17,15 @@ from .qcprot import CalcRMSDRotationalMatrix, get_rotation_matrix
 from .moments import second_order_moments
 from .rms import RMSF, Results
 from .pca import PCA, pca_from_comoment
+from .distances import DiffusionMap, DistanceMatrix
 
 __all__ = [
     "RMSF",
     "Results",
     "PCA",
     "pca_from_comoment",
+    "DistanceMatrix",
+    "DiffusionMap",
     "blocks",
     "second_order_moments",
     "get_rotation_matrix",

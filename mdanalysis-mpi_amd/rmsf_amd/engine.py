@@ -411,6 +411,37 @@ class Engine:
             raise ValueError("covariance_finish: buffer sizes")
         call("rmsf_covariance_finish", cov.data_ptr(), cov.stride(0), t1.data_ptr(), n_coord, n_frames, self.stream)
 
+    # -- all-pairs RMSD matrix (csrc/pairwise.hip) ----------------------------
+    def pairwise_centres(self, xyz_ptr: int, fstride: int, n_frames: int, n_sel: int, sel, weights,
+                         per_frame: bool = True):
+        """Every frame's weighted centre [n_frames, 3] and G_f = sum_a w_a
+        |x_f,a - c_f|^2 [n_frames] (rmsf_pairwise_centres).  ``per_frame``
+        False: frame 0's centre for every frame (the metric without
+        superposition; a common shift)."""
+        centre, g = self.empty(n_frames, 3), self.empty(n_frames)
+        call("rmsf_pairwise_centres", xyz_ptr, fstride, n_frames, n_sel, _ptr(sel), _ptr(weights), int(per_frame),
+             centre.data_ptr(), g.data_ptr(), self.stream)
+        return centre, g
+
+    def pairwise_workspace_bytes(self, n_frames: int, n_sel: int) -> int:
+        return int(self.lib.rmsf_pairwise_workspace_bytes(n_frames, n_sel))
+
+    def pairwise_rmsd(self, xyz_ptr: int, fstride: int, n_frames: int, n_sel: int, sel, weights, w_total: float,
+                      centre: torch.Tensor, g: torch.Tensor, out: torch.Tensor, superpose: bool = True,
+                      cutoff: float = 0.0, work: torch.Tensor | None = None) -> None:
+        """out[i, j] = out[j, i] = the RMSD of frames i and j (minimal over
+        rotations when ``superpose``), 0 where <= ``cutoff`` and on the
+        diagonal, on the f64 matrix cores (rmsf_pairwise_rmsd).  ``centre``,
+        ``g``: pairwise_centres' (per_frame = superpose).  ``work``: f64 scratch
+        of at least pairwise_workspace_bytes(n_frames, n_sel) bytes (None when 0)."""
+        if (out.dtype != F64 or centre.dtype != F64 or g.dtype != F64 or out.dim() != 2 or out.stride(1) != 1
+                or out.shape[0] < n_frames or out.shape[1] < n_frames or centre.numel() < 3 * n_frames
+                or g.numel() < n_frames or not centre.is_contiguous()):
+            raise ValueError("pairwise_rmsd: buffer sizes")
+        call("rmsf_pairwise_rmsd", xyz_ptr, fstride, n_frames, n_sel, _ptr(sel), _ptr(weights), float(w_total),
+             centre.data_ptr(), g.data_ptr(), int(bool(superpose)), float(cutoff), out.data_ptr(), out.stride(0),
+             _ptr(work), 0 if work is None else work.numel() * work.element_size(), self.stream)
+
     def qcp_batch(self, A: torch.Tensor, E0: torch.Tensor, N: torch.Tensor):
         n = A.shape[0]
         rot = self.empty(n, 9)

@@ -268,36 +268,47 @@ class RMSF:
         return self.results.rmsf
 
     def _make_source(self, eng: Engine):
-        x = self._input
-        if hasattr(x, "batches") and hasattr(x, "reference") and hasattr(x, "n_sel"):
-            return x, self.masses  # a frame source (DeviceSource, HostSource, XtcSource, ...)
-        if isinstance(x, torch.Tensor):
-            if x.device.type != "cuda":
-                x = x.detach().cpu().numpy()
-            else:
-                return DeviceSource(x, self.select, layout=self.layout), self.masses
-        # RMSF.py's two sweeps (align="average") read every frame twice
-        # (RMSF.py:92,124): host sources then keep the staged frames in HBM
-        two = self.align == "average"
-        if isinstance(x, np.ndarray):
-            return HostSource(x, self.select, batch_frames=self.batch_frames, cache=two,
-                              layout=self.layout), self.masses
-        if isinstance(x, (str, bytes)) or hasattr(x, "__fspath__"):
-            import os
-            path = os.fspath(x)
-            if str(path).lower().endswith(".dcd"):
-                # DCD frames are raw float32 planes: each batch's selected rows are
-                # read from the memory-mapped file and streamed through the stager
-                return DcdSource(path, self.select, batch_frames=self.batch_frames, cache=two), self.masses
-            if not str(path).lower().endswith(".xtc"):
-                raise ValueError(f"only .xtc and .dcd trajectory files are read natively, got {path!r}")
-            # aligned runs read the reference frame first (and RMSF.py's two sweeps read
-            # every frame twice): keep the decoded frames resident in HBM
-            return XtcSource(path, self.select, batch_frames=self.batch_frames,
-                             cache=self.align is not None), self.masses
-        if hasattr(x, "universe") and hasattr(x, "positions"):
-            masses = self.masses
-            if masses is None and self.align is not None:
-                masses = np.asarray(x.masses, dtype=np.float64)
-            return AtomGroupSource(x, batch_frames=self.batch_frames, cache=two), masses
-        raise TypeError(f"unsupported input {type(x)!r}: AtomGroup, numpy array or HIP torch tensor expected")
+        return make_source(self._input, select=self.select, masses=self.masses, align=self.align,
+                           batch_frames=self.batch_frames, layout=self.layout)
+
+
+def make_source(x, *, select=None, masses=None, align=None, batch_frames: int | None = None, layout: str = "fac",
+                group_masses: bool | None = None):
+    """The frame source of an analysis input -- a source itself, an
+    HBM-resident torch tensor, a host numpy array, the path of an ``.xtc`` or
+    ``.dcd`` file, or an MDAnalysis AtomGroup -- and the masses to use:
+    ``(source, masses)``.  ``align`` decides what host sources keep resident
+    (see below); ``group_masses`` whether an AtomGroup's masses stand in for
+    ``masses=None`` (default: for aligned runs).  Shared by ``RMSF`` and
+    ``DistanceMatrix``."""
+    if group_masses is None:
+        group_masses = align is not None
+    if hasattr(x, "batches") and hasattr(x, "reference") and hasattr(x, "n_sel"):
+        return x, masses  # a frame source (DeviceSource, HostSource, XtcSource, ...)
+    if isinstance(x, torch.Tensor):
+        if x.device.type != "cuda":
+            x = x.detach().cpu().numpy()
+        else:
+            return DeviceSource(x, select, layout=layout), masses
+    # RMSF.py's two sweeps (align="average") read every frame twice
+    # (RMSF.py:92,124): host sources then keep the staged frames in HBM
+    two = align == "average"
+    if isinstance(x, np.ndarray):
+        return HostSource(x, select, batch_frames=batch_frames, cache=two, layout=layout), masses
+    if isinstance(x, (str, bytes)) or hasattr(x, "__fspath__"):
+        import os
+        path = os.fspath(x)
+        if str(path).lower().endswith(".dcd"):
+            # DCD frames are raw float32 planes: each batch's selected rows are
+            # read from the memory-mapped file and streamed through the stager
+            return DcdSource(path, select, batch_frames=batch_frames, cache=two), masses
+        if not str(path).lower().endswith(".xtc"):
+            raise ValueError(f"only .xtc and .dcd trajectory files are read natively, got {path!r}")
+        # aligned runs read the reference frame first (and RMSF.py's two sweeps read
+        # every frame twice): keep the decoded frames resident in HBM
+        return XtcSource(path, select, batch_frames=batch_frames, cache=align is not None), masses
+    if hasattr(x, "universe") and hasattr(x, "positions"):
+        if masses is None and group_masses:
+            masses = np.asarray(x.masses, dtype=np.float64)
+        return AtomGroupSource(x, batch_frames=batch_frames, cache=two), masses
+    raise TypeError(f"unsupported input {type(x)!r}: AtomGroup, numpy array or HIP torch tensor expected")

@@ -54,7 +54,12 @@ def main(argv=None) -> int:
     ap.add_argument("--covariance", default=None, metavar="OUT.npy",
                     help="also write the positional covariance of the (aligned) selected coordinates, f64 "
                          "[3n, 3n] (co-moment / n_frames; not with --merge scatter), on rank 0")
+    ap.add_argument("--dist-matrix", default=None, metavar="OUT.npy",
+                    help="also write the all-pairs RMSD matrix of the selected atoms' frames, f64 [F, F] "
+                         "(rmsf_amd.DistanceMatrix; each pair superposed unless --align none; one process only)")
     a = ap.parse_args(argv)
+    if a.dist_matrix and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--dist-matrix runs in one process (no torch.distributed launch)")
     if a.covariance and a.merge == "scatter":
         ap.error("--covariance needs --merge root or all")
     if a.exact and (a.align != "none" or a.merge == "scatter"):
@@ -79,6 +84,7 @@ def main(argv=None) -> int:
     root = None if a.merge == "all" else 0
     cov_kw = {"covariance": True} if a.covariance else {}
     cov = None
+    dm_input, dm_kw = None, {}   # what --dist-matrix reads: the RMSF run's own input
     if a.synthetic:
         n_atoms, n_frames = a.synthetic
         eng = Engine()
@@ -92,6 +98,7 @@ def main(argv=None) -> int:
         rmsf = None if res.rmsf is None else res.rmsf.cpu().numpy()   # None on the non-root ranks
         if a.covariance and res.comoment is not None:
             cov = res.covariance.cpu().numpy()
+        dm_input = shard
     else:
         if not (a.topology and a.trajectory):
             ap.error("--topology/--trajectory (MDAnalysis) or --synthetic is required")
@@ -106,6 +113,7 @@ def main(argv=None) -> int:
                            merge_scatter=a.merge == "scatter", exact=a.exact,
                            merge_order=a.merge_order, **cov_kw).run().results
             rmsf, cov = results.rmsf, (results.covariance if a.covariance else None)
+            dm_input = ag
         else:
             # native fallback: GRO or PSF topology + selection subset; XTC, DCD (or
             # multi-frame GRO) trajectory.  PSF masses (GRO: masses guessed from
@@ -125,6 +133,12 @@ def main(argv=None) -> int:
                            verbose=True, merge_root=root, merge_scatter=a.merge == "scatter", exact=a.exact,
                            merge_order=a.merge_order, **cov_kw).run().results
             rmsf, cov = results.rmsf, (results.covariance if a.covariance else None)
+            dm_input, dm_kw = traj, {"select": sel, "weights": masses}
+    if a.dist_matrix:
+        from rmsf_amd import DistanceMatrix
+        dm = DistanceMatrix(dm_input, superposition=align is not None, **dm_kw).run().results
+        print(f"RMSD matrix over {dm.n_frames} frames: max {dm.dist_matrix.max():.6f} A", flush=True)
+        np.save(a.dist_matrix, dm.dist_matrix)
     if rank == 0:
         print(f"RMSF over {len(rmsf)} atoms: mean {rmsf.mean():.6f} A, max {rmsf.max():.6f} A", flush=True)
         if a.out:
