@@ -533,6 +533,42 @@ int rmsf_covariance_accumulate(const float *d_xyz, int64_t frame_stride,
 int rmsf_covariance_finish(double *d_cov, int64_t ld, const double *d_t1,
                            int64_t n_coord, int64_t n_frames, void *stream);
 
+/* ---- PCA projection (MDAnalysis.analysis.pca.PCA.transform) ----------------
+ * The projection of a batch's frames on n_comp components, a tall, skinny
+ * product [n_frames x 3 n_sel] . [3 n_sel x n_comp] on the f64 matrix cores
+ * (csrc/pca_project.hip).  Coordinate index i = 3 a + c over the selection's
+ * order (atom d_sel[a], or a when d_sel is NULL; rows only).  For every frame
+ * f of the batch:
+ *   p = the atom's three floats -- through the transform of RMSF.py:99-101 /
+ *       133-135 with the frame's record d_xform[f] and ref_com =
+ *       d_refinfo[0..2] when both are given (the device function the Welford
+ *       and covariance sweeps run: their coordinates bit for bit), the raw
+ *       floats when both are NULL;
+ *   d_i = f64(p_i) - d_mean[i]   (d_mean f64 [3 n_sel]);
+ *   d_out[f * ldo + c] = sum_i d_i d_comp[i * ldc + c],  c < n_comp
+ *       (d_comp f64 [3 n_sel][ldc >= n_comp], row i = coordinate i; d_out f64
+ *       [n_frames][ldo >= n_comp], overwritten; columns >= n_comp of either
+ *       are neither read nor written).
+ * Work is cut into (16 frames, panel of 48 components, coordinate range)
+ * workgroups, so each frame's bytes are read once for n_comp <= 48.  With
+ * more than one coordinate range (few frames, many atoms) the partials go to
+ * d_work (rmsf_pca_project_workspace_bytes() bytes, 0 when none is needed and
+ * d_work may be NULL) and are summed in coordinate order by a second launch:
+ * no floating-point atomics.  The plan is a function of (n_frames, n_sel,
+ * n_comp) alone: the same bits for the same inputs.
+ * rmsf_pca_project_workspace_bytes is host-only arithmetic (no device).
+ * Bad arguments (a NULL pointer, n_comp < 1, ldc or ldo < n_comp, one of
+ * d_xform and d_refinfo without the other, a workspace too small):
+ * RMSF_EINVAL.                                                              */
+size_t rmsf_pca_project_workspace_bytes(int64_t n_frames, int64_t n_sel,
+                                        int64_t n_comp);
+int rmsf_pca_project(const float *d_xyz, int64_t frame_stride,
+                     int64_t n_frames, int64_t n_sel, const int32_t *d_sel,
+                     const double *d_xform, const double *d_refinfo,
+                     const double *d_mean, const double *d_comp, int64_t ldc,
+                     int64_t n_comp, double *d_out, int64_t ldo, void *d_work,
+                     size_t work_bytes, void *stream);
+
 /* ---- all-pairs RMSD matrix (MDAnalysis.analysis.diffusionmap.DistanceMatrix)
  * The n_frames x n_frames matrix of RMSDs between every pair of frames of a
  * batch read at a constant frame_stride, on the f64 matrix cores

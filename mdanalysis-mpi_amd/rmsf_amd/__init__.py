@@ -7,7 +7,9 @@ Public surface (mirrors the reference's names):
     (device-backed versions of RMSF.py:36-51 and MDAnalysis.lib.qcprot)
   * ``blocks`` -- the RMSF.py:65-69 frame decomposition
   * ``PCA`` / ``pca_from_comoment`` -- the modes of the positional covariance
-    (``RMSF(..., covariance=True)``), named as MDAnalysis.analysis.pca.PCA names them
+    (``RMSF(..., covariance=True)``), named as MDAnalysis.analysis.pca.PCA names them;
+    ``PCA.transform`` projects a trajectory on them on the device, ``cosine_content``
+    measures such a projection's convergence
   * ``DistanceMatrix`` / ``DiffusionMap`` -- the all-pairs RMSD matrix of the frames and
     its diffusion map, named as MDAnalysis.analysis.diffusionmap names them
 """
@@ -16,7 +18,7 @@ from .parallel import blocks
 from .qcprot import CalcRMSDRotationalMatrix, get_rotation_matrix
 from .moments import second_order_moments
 from .rms import RMSF, Results
-from .pca import PCA, pca_from_comoment
+from .pca import PCA, cosine_content, pca_from_comoment
 from .distances import DiffusionMap, DistanceMatrix
 
 __all__ = [
@@ -24,6 +26,7 @@ __all__ = [
     "Results",
     "PCA",
     "pca_from_comoment",
+    "cosine_content",
     "DistanceMatrix",
     "DiffusionMap",
     "blocks",

@@ -411,6 +411,31 @@ class Engine:
             raise ValueError("covariance_finish: buffer sizes")
         call("rmsf_covariance_finish", cov.data_ptr(), cov.stride(0), t1.data_ptr(), n_coord, n_frames, self.stream)
 
+    # -- PCA projection (csrc/pca_project.hip) ---------------------------------
+    def pca_project_workspace_bytes(self, n_frames: int, n_sel: int, n_comp: int) -> int:
+        return int(self.lib.rmsf_pca_project_workspace_bytes(n_frames, n_sel, n_comp))
+
+    def pca_project(self, xyz_ptr: int, fstride: int, n_frames: int, n_sel: int, sel, xform, refinfo,
+                    mean: torch.Tensor, comp: torch.Tensor, n_comp: int, out: torch.Tensor,
+                    work: torch.Tensor | None = None) -> None:
+        """out[f, c] = sum_i d_i comp[i, c] for c < ``n_comp`` over the batch,
+        d = f64(p) - mean with p the selected rows -- through the transform of
+        RMSF.py:99-101 / 133-135 when ``xform`` and ``refinfo`` are given --
+        on the f64 matrix cores (rmsf_pca_project).  ``comp``: f64 [3 n_sel,
+        >= n_comp], ``out``: f64 [>= n_frames, >= n_comp], rows of either may
+        be wider (their other columns are not touched).  ``work``: f64 scratch
+        of at least pca_project_workspace_bytes(n_frames, n_sel, n_comp)
+        bytes (None when 0)."""
+        n = 3 * n_sel
+        if (mean.dtype != F64 or comp.dtype != F64 or out.dtype != F64 or comp.dim() != 2 or out.dim() != 2
+                or comp.stride(1) != 1 or out.stride(1) != 1 or mean.numel() < n or not mean.is_contiguous()
+                or comp.shape[0] < n or comp.shape[1] < n_comp or out.shape[0] < n_frames
+                or out.shape[1] < n_comp):
+            raise ValueError("pca_project: buffer sizes")
+        call("rmsf_pca_project", xyz_ptr, fstride, n_frames, n_sel, _ptr(sel), _ptr(xform), _ptr(refinfo),
+             mean.data_ptr(), comp.data_ptr(), comp.stride(0), n_comp, out.data_ptr(), out.stride(0), _ptr(work),
+             0 if work is None else work.numel() * work.element_size(), self.stream)
+
     # -- all-pairs RMSD matrix (csrc/pairwise.hip) ----------------------------
     def pairwise_centres(self, xyz_ptr: int, fstride: int, n_frames: int, n_sel: int, sel, weights,
                          per_frame: bool = True):

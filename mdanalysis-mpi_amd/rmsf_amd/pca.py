@@ -8,8 +8,16 @@ matrix on the device (csrc/covariance.hip, the f64 matrix cores) from the
 very coordinates the Welford sweep reads; the eigen-decomposition of the
 [3n, 3n] f64 matrix is ``numpy.linalg.eigh`` on the host.
 
-``transform()`` -- the projection of a trajectory on the components -- is not
-part of this module.
+``PCA.transform()`` projects a trajectory on the components, on the device
+(csrc/pca_project.hip, the f64 matrix cores again): every frame is superposed
+as the run's last sweep superposed it -- the same kernels, masses and
+reference -- and the deviations from ``results.mean`` are contracted with the
+components, batch by batch, with no aligned copy of the trajectory anywhere.
+``cosine_content`` is the usual convergence measure of such a projection.
+
+MDAnalysis is not a dependency and is absent where this was written: the
+semantics of ``transform`` and ``cosine_content`` are restated from its
+published documentation, not verified against it.
 """
 from __future__ import annotations
 
@@ -42,6 +50,67 @@ def pca_from_comoment(comoment, n_frames: int, ddof: int = 1, n_components: int 
     return np.ascontiguousarray(v[:, :k]), w[:k].copy(), cumulated[:k].copy()
 
 
+def _simpson(y: np.ndarray) -> float:
+    """Simpson's rule over samples one unit apart: the composite 1/3 rule,
+    closed with one 3/8 panel when the number of intervals is odd (the
+    trapezoid for two samples)."""
+    y = np.asarray(y, dtype=np.float64)
+    n = y.size - 1  # intervals
+    if n < 1:
+        return 0.0
+    if n == 1:
+        return 0.5 * (y[0] + y[1])
+    tail = 0.0
+    if n % 2:
+        tail = 3.0 / 8.0 * (y[-4] + 3.0 * y[-3] + 3.0 * y[-2] + y[-1])
+        y = y[:-3]
+        if y.size < 3:
+            return tail
+    return float((y[0] + 4.0 * y[1:-1:2].sum() + 2.0 * y[2:-1:2].sum() + y[-1]) / 3.0 + tail)
+
+
+def cosine_content(pca_space, i: int) -> float:
+    """The cosine content of column ``i`` of a ``PCA.transform`` output
+    [n_frames, k]:
+
+        2 / T  (int_0^T cos(pi (i + 1) t / T) p_i(t) dt)^2 / int_0^T p_i(t)^2 dt
+
+    with t the frame number and T = n_frames - 1 the length of the
+    trajectory, both integrals by Simpson's rule (numpy only).  1 for a
+    projection that is exactly the half-period cosine of its index -- the
+    signature of random diffusion, i.e. of an unconverged simulation -- and
+    near 0 for a converged one (B. Hess, Phys Rev E 65:031910, 2002).
+    Restated from MDAnalysis' documentation of
+    ``MDAnalysis.analysis.pca.cosine_content``, not verified against it."""
+    p = np.asarray(pca_space, dtype=np.float64)
+    if p.ndim != 2:
+        raise ValueError("pca_space must be [n_frames, n_components]")
+    if not 0 <= int(i) < p.shape[1]:
+        raise ValueError(f"i must be in 0..{p.shape[1] - 1}, got {i}")
+    if p.shape[0] < 2:
+        raise ValueError("cosine_content needs at least 2 frames")
+    col = p[:, int(i)]
+    big_t = float(p.shape[0] - 1)
+    cos = np.cos(np.pi * (int(i) + 1) * np.arange(p.shape[0]) / big_t)
+    return float(2.0 / big_t * _simpson(cos * col) ** 2 / _simpson(col * col))
+
+
+_ONE_DEVICE = "PCA.transform runs on one device per process: not "
+_PLANES = ('PCA.transform reads (frame, atom, xyz) rows; HBM-resident coordinate planes are not supported -- pass '
+           'the trajectory with layout="fac"')
+
+
+def check_projection_memory(eng, n_frames: int, n_comp: int) -> None:
+    """MemoryError if the [F, k] f64 projection is over half the free HBM."""
+    import torch
+
+    need = 8 * n_frames * n_comp
+    free = torch.cuda.mem_get_info(eng.device)[0]
+    if need > free // 2:
+        raise MemoryError(f"PCA.transform: the [{n_frames}, {n_comp}] f64 projection needs {need} bytes, over half "
+                          f"of the {free} bytes of free HBM")
+
+
 class PCA:
     """Principal component analysis of a trajectory's selected coordinates.
 
@@ -58,6 +127,9 @@ class PCA:
     and ``results.n_frames``.  Coordinate order 3 a + c over the selection's
     order.  Under ``torch.distributed`` with ``merge_root`` the other ranks'
     results are None.
+
+    ``transform()`` then gives the projection of the trajectory (or of
+    another one) on the components, f64 [n_frames, k].
     """
 
     def __init__(self, atomgroup, select=None, align="average", n_components: int | None = None, ddof: int = 1,
@@ -81,3 +153,144 @@ class PCA:
         out.covariance = r.comoment / float(r.n_frames - self.ddof)
         self.n_frames = r.n_frames
         return self
+
+    def _refuse_transform(self, atomgroup) -> None:
+        import torch
+
+        from . import parallel
+        from .sources import DeviceSource
+
+        r = self._rmsf
+        for x in (r._input, atomgroup):
+            if isinstance(x, (list, tuple)):
+                raise NotImplementedError(_ONE_DEVICE + "with gpus= or a list of shards")
+        if r.gpus is not None:
+            raise NotImplementedError(_ONE_DEVICE + "with gpus= or a list of shards")
+        x = r._input if atomgroup is None else atomgroup
+        if (isinstance(x, DeviceSource) and x.layout == "soa") or (
+                isinstance(x, torch.Tensor) and x.device.type == "cuda" and r.layout == "soa"):
+            raise NotImplementedError(_PLANES)
+        if parallel.world()[1] > 1:
+            raise NotImplementedError(_ONE_DEVICE + "under torch.distributed with more than one rank")
+
+    def transform(self, atomgroup=None, n_components: int | None = None, start=None, stop=None, step=None,
+                  frames=None, as_tensor: bool = False):
+        """The projection of a trajectory on the first ``n_components``
+        components (default: all that ``run()`` computed): host f64
+        [n_frames, n_components], or the HBM tensor with ``as_tensor=True``.
+
+            proj[f, c] = sum_i (x_i(f) - results.mean_i) results.p_components[i, c]
+
+        ``atomgroup=None``: the input ``run()`` read, and its frame list
+        unless ``start``/``stop``/``step``/``frames`` give another.  Any other
+        input takes what ``RMSF`` takes, with the PCA's ``select``, ``masses``
+        and ``layout``, and must select as many atoms (ValueError).
+
+        With ``align`` set, each frame x(f) is superposed exactly as the run's
+        last sweep superposed it: the same masses, the same device reference
+        (the all-reduced average, or frame ``ref_frame`` of the run's
+        trajectory), the same entry points -- rmsf_superpose on the
+        frame-parallel path, rmsf_superpose_sequential when the run was exact
+        -- and the same f32 transform inside the projection kernel, so the
+        trajectory ``run()`` read is projected from the very bits its
+        covariance was formed from.  Frames stream through in batches of
+        ``batch_frames``; a dense HBM tensor is read in place.  ``run()``'s
+        source stays alive on the PCA for this (a host input's staged frames
+        in HBM included).  Results filled in by hand (components kept from
+        an earlier session) can be projected on without a ``run()`` only for
+        ``align=None``: there is no superposition to repeat.
+
+        One device per process: ``gpus=``, lists of shards, HBM-resident
+        ``layout="soa"`` planes and a ``torch.distributed`` world of more than
+        one rank are NotImplementedError; a projection over half the free HBM
+        is a MemoryError."""
+        comps = self.results.get("p_components")
+        if comps is None:
+            raise ValueError("PCA.transform needs the components: call run() first (the non-root ranks of a "
+                             "reduce-to-root merge hold none)")
+        k_total = int(comps.shape[1])
+        k = k_total if n_components is None else int(n_components)
+        if not 1 <= k <= k_total:
+            raise ValueError(f"n_components must be in 1..{k_total}, got {n_components}")
+        self._refuse_transform(atomgroup)
+        r = self._rmsf
+        last = r._last_run
+        if last is None:
+            # results filled in by hand (components kept from an earlier run): without alignment there is
+            # no superposition to repeat, and the PCA's own input can be projected
+            if r.align is not None:
+                raise ValueError("PCA.transform needs the superposition of run(): these results were not computed "
+                                 "by run() on this object")
+            last = {"source": None, "frames": None, "masses": None, "device": r.device, "exact": False,
+                    "ref": None, "refinfo": None}
+
+        import torch
+
+        from ._lib import RMSF_XFORM_DOUBLES
+        from .engine import Engine
+        from .pipeline import Superposer
+        from .rms import make_source
+        from .sources import DeviceSource, FrameList
+
+        eng = Engine(last["device"])
+        with torch.cuda.device(eng.device):
+            if atomgroup is None and last["source"] is None:
+                atomgroup = r._input
+            if atomgroup is None:
+                src = last["source"]
+                same = start is None and stop is None and step is None and frames is None
+                fl = last["frames"] if same else FrameList(src.n_traj, start, stop, step, frames=frames)
+            else:
+                src, _ = make_source(atomgroup, select=r.select, masses=r.masses, align=None,
+                                     batch_frames=r.batch_frames, layout=r.layout, group_masses=False)
+                fl = FrameList(src.n_traj, start, stop, step, frames=frames)
+            if isinstance(src, DeviceSource) and src.layout == "soa":
+                raise NotImplementedError(_PLANES)
+            n_sel = src.n_sel
+            if 3 * n_sel != comps.shape[0]:
+                raise ValueError(f"the input selects {n_sel} atoms, the components were computed for "
+                                 f"{comps.shape[0] // 3}")
+            n_frames = len(fl)
+            check_projection_memory(eng, n_frames, k)
+            out = eng.empty(n_frames, k)
+            if n_frames == 0:
+                return out if as_tensor else out.cpu().numpy()
+            mean = torch.as_tensor(np.ascontiguousarray(self.results.mean, dtype=np.float64).reshape(-1)).to(
+                eng.device)
+            comp = torch.as_tensor(np.ascontiguousarray(comps, dtype=np.float64)).to(eng.device)
+            max_batch = max(1, min(r.batch_frames or n_frames, n_frames))
+            aligned = r.align is not None
+            exact = bool(last["exact"])
+            ref, info = last["ref"], last["refinfo"]
+            m_dev, mass_total, sup, xf = None, float(n_sel), None, None
+            if aligned:
+                masses = last["masses"]
+                if masses is not None:
+                    m_np = np.ascontiguousarray(masses, dtype=np.float64)
+                    mass_total = float(m_np.sum())  # numpy's own sum, as the exact run's (pipeline._run_exact)
+                    m_dev = torch.as_tensor(m_np).to(eng.device)
+                if exact:
+                    xf = eng.empty(max_batch, RMSF_XFORM_DOUBLES)
+                else:
+                    sup = Superposer(eng, n_sel, max_batch, m_dev)
+            work, done = None, 0
+            for b in src.batches(fl, 0, n_frames, max_batch, eng.stream):
+                if b.pstride:
+                    raise NotImplementedError(_PLANES)
+                x = None
+                if aligned and exact:
+                    x = xf[:b.n_frames]
+                    eng.superpose_seq(b.ptr, b.fstride, b.n_frames, n_sel, b.sel, m_dev, mass_total, ref, info, x)
+                elif aligned:
+                    x = sup.run(b, ref, info)
+                need = eng.pca_project_workspace_bytes(b.n_frames, n_sel, k)
+                if need and (work is None or need > work.numel() * 8):  # not monotone in the batch size
+                    work = eng.empty((need + 7) // 8)
+                eng.pca_project(b.ptr, b.fstride, b.n_frames, n_sel, b.sel, x, info if x is not None else None,
+                                mean, comp, k, out[done:done + b.n_frames], work if need else None)
+                done += b.n_frames
+                b.done()
+            if done != n_frames:
+                raise RuntimeError(f"the source yielded {done} of {n_frames} frames")
+            torch.cuda.current_stream(eng.device).synchronize()
+            return out if as_tensor else out.cpu().numpy()

@@ -806,7 +806,9 @@ def run_pipeline(eng: Engine, source, frames: FrameList, *, align=None, masses=N
     return PipelineResult(rmsf=rmsf, mean=mean.view(n_sel, 3), m2=m2.view(n_sel, 3), n_frames=n_total,
                           n_local=n_local, block=(b0, b1),
                           average=None if average is None else average.view(n_sel, 3), rmsd=rmsd,
-                          transforms=xf_last, transforms_sweep1=xf_first, comoment=comoment)
+                          transforms=xf_last, transforms_sweep1=xf_first, comoment=comoment,
+                          # the last sweep's device reference (None unaligned), for PCA.transform
+                          extras={"exact": False, "ref": ref, "refinfo": info})
 
 
 EXACT_OVERLAP_MIN_ATOMS = 16384
@@ -962,7 +964,8 @@ def _run_exact(eng: Engine, source, frames: FrameList, max_batch, block, timer, 
                           m2=None if ss is None else ss.view(n_sel, 3), n_frames=n_total, n_local=n_local,
                           block=(b0, b1), average=None if average is None else average.view(n_sel, 3), rmsd=rmsd,
                           transforms=xf_last, transforms_sweep1=xf_first,
-                          extras={"exact": True, "merge_root": root, "merge_order": merge_order}, comoment=comoment)
+                          extras={"exact": True, "merge_root": root, "merge_order": merge_order, "ref": ref,
+                                  "refinfo": info}, comoment=comoment)
 
 
 class UploadedMasses:

@@ -187,6 +187,7 @@ class RMSF:
         self.gpus = gpus
         self.results = Results()
         self._source = None
+        self._last_run = None
 
     # MDAnalysis AnalysisBase compatible signature
     def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
@@ -218,6 +219,12 @@ class RMSF:
                                collect_transforms=self.collect_transforms, merge_root=self.merge_root,
                                merge_scatter=self.merge_scatter, exact=self.exact, merge_order=self.merge_order,
                                **({"covariance": True} if self.covariance else {}))
+            if self.covariance:
+                # what PCA.transform superposes with, exactly as the last sweep did: its source and frame
+                # list, the masses, the device reference and whether the sequential kernels ran
+                self._last_run = {"source": src, "frames": fl, "masses": masses, "device": eng.device,
+                                  "exact": bool(res.extras.get("exact", False)), "ref": res.extras.get("ref"),
+                                  "refinfo": res.extras.get("refinfo")}
             torch.cuda.current_stream(eng.device).synchronize()
             r = self.results
             host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731  (None: a non-root rank)

@@ -57,7 +57,16 @@ def main(argv=None) -> int:
     ap.add_argument("--dist-matrix", default=None, metavar="OUT.npy",
                     help="also write the all-pairs RMSD matrix of the selected atoms' frames, f64 [F, F] "
                          "(rmsf_amd.DistanceMatrix; each pair superposed unless --align none; one process only)")
+    ap.add_argument("--pca-transform", default=None, metavar="OUT.npy",
+                    help="also run rmsf_amd.PCA on the same input with --align and write the projection of the "
+                         "frames on its components, f64 [F, K] (PCA.transform; one process only)")
+    ap.add_argument("--n-components", type=int, default=None, metavar="K",
+                    help="--pca-transform: the number of components (default: all 3n)")
     a = ap.parse_args(argv)
+    if a.pca_transform and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--pca-transform runs in one process (no torch.distributed launch)")
+    if a.pca_transform and a.merge == "scatter":
+        ap.error("--pca-transform needs --merge root or all")
     if a.dist_matrix and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--dist-matrix runs in one process (no torch.distributed launch)")
     if a.covariance and a.merge == "scatter":
@@ -139,6 +148,14 @@ def main(argv=None) -> int:
         dm = DistanceMatrix(dm_input, superposition=align is not None, **dm_kw).run().results
         print(f"RMSD matrix over {dm.n_frames} frames: max {dm.dist_matrix.max():.6f} A", flush=True)
         np.save(a.dist_matrix, dm.dist_matrix)
+    if a.pca_transform:
+        from rmsf_amd import PCA
+        pca_kw = {"select": dm_kw["select"], "masses": dm_kw["weights"]} if dm_kw else {}
+        pca = PCA(dm_input, align=align, ref_frame=a.ref_frame, n_components=a.n_components, **pca_kw).run()
+        proj = pca.transform()
+        print(f"PCA projection of {proj.shape[0]} frames on {proj.shape[1]} components: the first holds "
+              f"{pca.results.cumulated_variance[0]:.4f} of the variance", flush=True)
+        np.save(a.pca_transform, proj)
     if rank == 0:
         print(f"RMSF over {len(rmsf)} atoms: mean {rmsf.mean():.6f} A, max {rmsf.max():.6f} A", flush=True)
         if a.out:
