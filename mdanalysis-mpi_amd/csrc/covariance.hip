@@ -19,41 +19,22 @@
 //   * k_cov_finish  M = C - T1 T1^T / N, mirrored to the full matrix.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
-#include <string>
 
-#include "rmsf_hip.h"
+#include "dense_f64.h"
 #include "rmsf_device.h"
-
-#define RMSF_EXPORT __attribute__((visibility("default")))
-
-extern "C" int rmsf_internal_set_error(int code, const char *msg);
+#include "rmsf_host.h"
 
 namespace {
 
-int fail(int code, const std::string &m) { return rmsf_internal_set_error(code, m.c_str()); }
-
-int after_launch(const char *what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(RMSF_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return RMSF_OK;
-}
-
-inline hipStream_t S(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
-
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kXform = RMSF_XFORM_DOUBLES;
 constexpr int kTA = 16;                // atoms a side of a macro tile
 constexpr int kTC = 3 * kTA;           // coordinates a side: 3 MFMA tiles
 constexpr int kKT = 32;                // frames staged at a time (8 per wave: 2 MFMA k-steps)
 constexpr int kTile = kTC * kTC;       // results of a macro tile pair
-constexpr int kRec = 12;               // doubles of a transform record apply_xform reads
 constexpr int kFrameLanes = kBlock / kTA;  // frames staged per pass (one atom per lane)
-constexpr int64_t kTargetGroups = 512;     // 2 resident workgroups (156-182 VGPRs) per CU on MI355X
+constexpr int64_t kTargetGroups = 512;     // 2 resident workgroups (152-200 VGPRs) per CU on MI355X
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
+static_assert(sizeof(double) * (2 * kKT * kTC + kFrameLanes * kTC + kKT * kRec) <= kLdsLimit, "sm, st1 and sxf fit");
 
 // The work decomposition, a function of (n_sel, n_frames) alone, so the
 // workspace layout and the summation order are fixed by the batching.
@@ -68,11 +49,9 @@ CovPlan cov_plan(int64_t n_sel, int64_t n_frames) {
   CovPlan p;
   p.n_tiles = (n_sel + kTA - 1) / kTA;
   p.n_pairs = p.n_tiles * (p.n_tiles + 1) / 2;
-  const int64_t stages = std::max<int64_t>(1, (n_frames + kKT - 1) / kKT);
-  int64_t ks = std::max<int64_t>(1, std::min<int64_t>(stages, kTargetGroups / p.n_pairs));
-  const int64_t per = (stages + ks - 1) / ks;
-  p.n_ks = (stages + per - 1) / per;
-  p.ks_frames = per * kKT;
+  const SplitK k = split_k(std::max<int64_t>(1, (n_frames + kKT - 1) / kKT), p.n_pairs, kTargetGroups, 1);
+  p.n_ks = k.n_ks;
+  p.ks_frames = k.per * kKT;
   return p;
 }
 
@@ -81,23 +60,10 @@ size_t cov_work_doubles(const CovPlan &p) {
   return (size_t)p.n_ks * ((size_t)p.n_pairs * kTile + (size_t)p.n_tiles * kTC);
 }
 
-// pair index -> (I, J), J >= I, rows of the upper block triangle in order
-__device__ __forceinline__ void pair_to_tiles(int64_t p, int64_t n_tiles, int64_t &I, int64_t &J) {
-  int64_t i = 0;
-  while (p >= n_tiles - i) {
-    p -= n_tiles - i;
-    ++i;
-  }
-  I = i;
-  J = i + p;
-}
-
 // One workgroup: tile pair blockIdx.x, frames [blockIdx.y ks_frames, ...).
 // Staging: lane (tid & 15) owns one atom of the tile, (tid >> 4) one of 16
-// frames per pass; its three deviations go to sm[op][k][3 atom + c].  MFMA
-// operands (16x16x4 f64): lane l holds A[i = l & 15][k = l >> 4] and
-// B[k = l >> 4][j = l & 15], i.e. 16 consecutive doubles of row k each; the
-// result D has col = l & 15, row = (l >> 4) + 4 reg.
+// frames per pass; its three deviations go to sm[op][k][3 atom + c], so an
+// MFMA operand (mfma_3x3, dense_f64.h) is 16 consecutive doubles of row k.
 template <bool ALIGN, bool GATHER>
 __global__ __launch_bounds__(kBlock, 2) void k_cov_tiles(const float *__restrict__ xyz, int64_t fstride,
                                                       int64_t n_frames, int64_t n_sel,
@@ -144,10 +110,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_cov_tiles(const float *__restrict
   const double rc0 = ALIGN ? refinfo[0] : 0.0, rc1 = ALIGN ? refinfo[1] : 0.0, rc2 = ALIGN ? refinfo[2] : 0.0;
 
   f64x4 acc[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
+  zero_3x3(acc);
   double ts[3] = {0.0, 0.0, 0.0};  // the lane's share of T1 (operand A, its frames in order)
 
   const double *sA = sm;
@@ -226,36 +189,15 @@ __global__ __launch_bounds__(kBlock, 2) void k_cov_tiles(const float *__restrict
       const double *__restrict__ rb = sB + k * kTC + (lane & 15);
       const double a0 = ra[0], a1 = ra[16], a2 = ra[32];
       const double b0 = rb[0], b1 = rb[16], b2 = rb[32];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-      acc[0][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b2, acc[0][2], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-      acc[1][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b2, acc[1][2], 0, 0, 0);
-      acc[2][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b0, acc[2][0], 0, 0, 0);
-      acc[2][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b1, acc[2][1], 0, 0, 0);
-      acc[2][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, acc[2][2], 0, 0, 0);
+      mfma_3x3(acc, a0, a1, a2, b0, b1, b2);
     }
     park_records();  // this stage's were last read before the barrier above
     __syncthreads();
   }
 
-  // ---- the four waves' accumulators, summed in wave order through LDS
-  // (every wave maps lane -> element alike, so a lane only meets its own)
-  for (int w = 0; w < kWaves; ++w) {
-    if (wave == w) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int e = (16 * i + (lane >> 4) + 4 * r) * kTC + 16 * j + (lane & 15);
-            sm[e] = w == 0 ? acc[i][j][r] : sm[e] + acc[i][j][r];
-          }
-    }
-    __syncthreads();
-  }
+  // ---- the four waves' accumulators, summed in wave order: row-major [kTC][kTC]
+  wave_sum_3x3(acc, sm, lane, wave,
+               [](int i, int j, int row, int col) { return (16 * i + row) * kTC + 16 * j + col; });
   if (diag) st1[tf * kTC + 3 * ta] = ts[0], st1[tf * kTC + 3 * ta + 1] = ts[1], st1[tf * kTC + 3 * ta + 2] = ts[2];
   __syncthreads();
 
@@ -341,6 +283,11 @@ __global__ __launch_bounds__(kBlock) void k_cov_finish(double *__restrict__ cov,
 }  // namespace
 
 extern "C" {
+
+// (for the tests: the tile mapping of this kernel and pairwise.hip's, on the host)
+RMSF_EXPORT void rmsf_internal_pair_to_tiles(int64_t p, int64_t n_tiles, int64_t *I, int64_t *J) {
+  pair_to_tiles(p, n_tiles, *I, *J);
+}
 
 RMSF_EXPORT size_t rmsf_covariance_workspace_bytes(int64_t n_sel, int64_t n_frames) {
   if (n_sel < 1 || n_frames < 1) return 0;

@@ -28,31 +28,15 @@
 //                   superposition), the cutoff, the store and its mirror.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <string>
 
-#include "rmsf_hip.h"
-
-#define RMSF_EXPORT __attribute__((visibility("default")))
-
-extern "C" int rmsf_internal_set_error(int code, const char *msg);
+#include "dense_f64.h"
+#include "rmsf_device.h"
+#include "rmsf_host.h"
 
 namespace {
 
-int fail(int code, const std::string &m) { return rmsf_internal_set_error(code, m.c_str()); }
-
-int after_launch(const char *what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(RMSF_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return RMSF_OK;
-}
-
-inline hipStream_t S(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
-
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
 constexpr int kTF = 16;                    // frames a side of a macro tile
 constexpr int kTC = 3 * kTF;               // rows a side: 3 MFMA tiles (x, y, z of the 16 frames)
 constexpr int kKA = 32;                    // atoms staged at a time (8 per wave: 2 MFMA k-steps)
@@ -66,8 +50,7 @@ constexpr int64_t kTargetGroups = 512;     // 2 resident workgroups per CU on MI
 
 static_assert(kPairs == kBlock, "the epilogue gives every thread one frame pair");
 static_assert(kTile <= 2 * kKA * kPitch, "the waves' sum reuses the staging buffer");
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
+static_assert(sizeof(double) * (2 * kKA * kPitch + kTF * (kTF + 1)) <= kLdsLimit, "sm and sd fit");
 
 // The work decomposition, a function of (n_frames, n_sel) alone, so the
 // workspace layout and the summation order are fixed by the sizes.
@@ -82,31 +65,15 @@ PwPlan pw_plan(int64_t n_frames, int64_t n_sel) {
   PwPlan p;
   p.n_tiles = (n_frames + kTF - 1) / kTF;
   p.n_pairs = p.n_tiles * (p.n_tiles + 1) / 2;
-  const int64_t stages = std::max<int64_t>(1, (n_sel + kKA - 1) / kKA);
-  const int64_t ks = std::max<int64_t>(1, std::min<int64_t>(stages, kTargetGroups / p.n_pairs));
-  const int64_t per = (stages + ks - 1) / ks;
-  p.n_ks = (stages + per - 1) / per;
-  p.ks_atoms = per * kKA;
+  const SplitK k = split_k(std::max<int64_t>(1, (n_sel + kKA - 1) / kKA), p.n_pairs, kTargetGroups, 1);
+  p.n_ks = k.n_ks;
+  p.ks_atoms = k.per * kKA;
   return p;
 }
 
 size_t pw_work_doubles(const PwPlan &p) {
   if (p.n_ks <= 1) return 0;
   return (size_t)p.n_ks * (size_t)p.n_pairs * kTile;
-}
-
-// pair index -> (I, J), J >= I, rows of the upper block triangle in order.
-// Row I starts at I n - I (I - 1) / 2; the root of that quadratic, then a
-// step either way for its rounding.
-__device__ __forceinline__ void pair_to_tiles(int64_t p, int64_t n_tiles, int64_t &I, int64_t &J) {
-  const double b = 2.0 * (double)n_tiles + 1.0;
-  int64_t i = (int64_t)((b - sqrt(b * b - 8.0 * (double)p)) * 0.5);
-  if (i < 0) i = 0;
-  if (i > n_tiles - 1) i = n_tiles - 1;
-  while (i > 0 && i * n_tiles - i * (i - 1) / 2 > p) --i;
-  while (i + 1 < n_tiles && (i + 1) * n_tiles - (i + 1) * i / 2 <= p) ++i;
-  I = i;
-  J = i + (p - (i * n_tiles - i * (i - 1) / 2));
 }
 
 // Sum of v over the workgroup in a fixed order (a halving tree over LDS);
@@ -158,56 +125,6 @@ __global__ __launch_bounds__(kBlock) void k_pw_centres(const float *__restrict__
   }
 }
 
-// The largest root of the QCP quartic (Theobald, Acta Cryst A 61:478, 2005;
-// Liu et al., J Comput Chem 31:1561, 2010): the coefficients, the start
-// lambda = E0 and the stopping rule of qcp_solve (rmsf_device.h), without the
-// rotation.  A is the row-major 3 x 3 inner product.
-__device__ __forceinline__ double qcp_lambda(const double *A, double E0) {
-  const double Sxx = A[0], Sxy = A[1], Sxz = A[2];
-  const double Syx = A[3], Syy = A[4], Syz = A[5];
-  const double Szx = A[6], Szy = A[7], Szz = A[8];
-
-  const double Sxx2 = Sxx * Sxx, Syy2 = Syy * Syy, Szz2 = Szz * Szz;
-  const double Sxy2 = Sxy * Sxy, Syz2 = Syz * Syz, Sxz2 = Sxz * Sxz;
-  const double Syx2 = Syx * Syx, Szy2 = Szy * Szy, Szx2 = Szx * Szx;
-
-  const double SyzSzymSyySzz2 = 2.0 * (Syz * Szy - Syy * Szz);
-  const double Sxx2Syy2Szz2Syz2Szy2 = Syy2 + Szz2 - Sxx2 + Syz2 + Szy2;
-
-  const double C2 = -2.0 * (Sxx2 + Syy2 + Szz2 + Sxy2 + Syx2 + Sxz2 + Szx2 + Syz2 + Szy2);
-  const double C1 = 8.0 * (Sxx * Syz * Szy + Syy * Szx * Sxz + Szz * Sxy * Syx - Sxx * Syy * Szz -
-                           Syz * Szx * Sxy - Szy * Syx * Sxz);
-
-  const double SxzpSzx = Sxz + Szx, SyzpSzy = Syz + Szy, SxypSyx = Sxy + Syx;
-  const double SyzmSzy = Syz - Szy, SxzmSzx = Sxz - Szx, SxymSyx = Sxy - Syx;
-  const double SxxpSyy = Sxx + Syy, SxxmSyy = Sxx - Syy;
-  const double Sxy2Sxz2Syx2Szx2 = Sxy2 + Sxz2 - Syx2 - Szx2;
-
-  const double C0 =
-      Sxy2Sxz2Syx2Szx2 * Sxy2Sxz2Syx2Szx2 +
-      (Sxx2Syy2Szz2Syz2Szy2 + SyzSzymSyySzz2) * (Sxx2Syy2Szz2Syz2Szy2 - SyzSzymSyySzz2) +
-      (-(SxzpSzx) * (SyzmSzy) + (SxymSyx) * (SxxmSyy - Szz)) *
-          (-(SxzmSzx) * (SyzpSzy) + (SxymSyx) * (SxxmSyy + Szz)) +
-      (-(SxzpSzx) * (SyzpSzy) - (SxypSyx) * (SxxpSyy - Szz)) *
-          (-(SxzmSzx) * (SyzmSzy) - (SxypSyx) * (SxxpSyy + Szz)) +
-      (+(SxypSyx) * (SyzpSzy) + (SxzpSzx) * (SxxmSyy + Szz)) *
-          (-(SxymSyx) * (SyzmSzy) + (SxzpSzx) * (SxxpSyy + Szz)) +
-      (+(SxypSyx) * (SyzmSzy) + (SxzmSzx) * (SxxmSyy - Szz)) *
-          (-(SxymSyx) * (SyzpSzy) + (SxzmSzx) * (SxxpSyy - Szz));
-
-  double l = E0;
-  for (int i = 0; i < 50; ++i) {
-    const double old = l;
-    const double x2 = l * l;
-    const double b = (x2 + C2) * l;
-    const double a = b + C1;
-    const double delta = (a * l + C0) / (2.0 * x2 * l + b + a);
-    l -= delta;
-    if (fabs(l - old) < fabs(1e-11 * l)) break;
-  }
-  return l;
-}
-
 // Thread tid owns the frame pair (fi = tid >> 4 of tile I, fj = tid & 15 of
 // tile J) and its A_ij.  Pairs j > i are computed; each value goes to [i, j]
 // and, through LDS so that both stores run along rows, to [j, i]; the
@@ -225,6 +142,7 @@ __device__ __forceinline__ void pair_epilogue(const double *A, int64_t I, int64_
     const double gi = g[i], gj = g[j];
     const double E0 = (gi + gj) * 0.5;
     if (superpose) {
+      // lambda as qcp_solve finds it (rmsf_device.h), without the rotation
       // (two all-zero frames: the quartic is 0 / 0; their distance is 0)
       const double l = E0 > 0.0 || E0 != E0 ? qcp_lambda(A, E0) : E0;
       d = sqrt(fabs(2.0 * (E0 - l)) / w_total);
@@ -251,11 +169,10 @@ __device__ __forceinline__ void pair_epilogue(const double *A, int64_t I, int64_
 // One workgroup: tile pair blockIdx.x, atoms [blockIdx.y ks_atoms, ...).
 // Staging: lane (tid & 15) walks the atoms of frame (tid >> 4) of the tile;
 // its three deviations f64(x) - c_f go to sm[op][atom k][16 c + frame]
-// (operand A times the atom's weight).  MFMA operands (16x16x4 f64): lane l
-// holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15], i.e. 16
-// consecutive doubles of staged atom k each; the result D has col = l & 15,
-// row = (l >> 4) + 4 reg -- so acc[ci][cj][reg] of lane l is entry (ci, cj)
-// of A_ij for frames i = (l >> 4) + 4 reg of tile I and j = l & 15 of tile J.
+// (operand A times the atom's weight), so an MFMA operand (mfma_3x3,
+// dense_f64.h) is 16 consecutive doubles of staged atom k, and
+// acc[ci][cj][reg] of lane l is entry (ci, cj) of A_ij for frames
+// i = (l >> 4) + 4 reg of tile I and j = l & 15 of tile J.
 template <bool GATHER, bool WEIGHTED>
 __global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict__ xyz, int64_t fstride,
                                                      int64_t n_frames, int64_t n_sel,
@@ -298,10 +215,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict_
   }
 
   f64x4 acc[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
+  zero_3x3(acc);
 
   const double *sA = sm;
   const double *sB = n_ops == 1 ? sm : sm + kKA * kPitch;
@@ -356,37 +270,15 @@ __global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict_
       const double *__restrict__ rb = sB + k * kPitch + (lane & 15);
       const double x0 = ra[0], x1 = ra[kTF], x2 = ra[2 * kTF];
       const double y0 = rb[0], y1 = rb[kTF], y2 = rb[2 * kTF];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y1, acc[0][1], 0, 0, 0);
-      acc[0][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y2, acc[0][2], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y1, acc[1][1], 0, 0, 0);
-      acc[1][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y2, acc[1][2], 0, 0, 0);
-      acc[2][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, y0, acc[2][0], 0, 0, 0);
-      acc[2][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, y1, acc[2][1], 0, 0, 0);
-      acc[2][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, y2, acc[2][2], 0, 0, 0);
+      mfma_3x3(acc, x0, x1, x2, y0, y1, y2);
     }
     __syncthreads();
   }
 
-  // ---- the four waves' accumulators, summed in wave order through LDS
-  // (every wave maps lane -> element alike, so a lane only meets its own).
-  // Entry q = 3 ci + cj of the pair (fi = (lane >> 4) + 4 reg, fj = lane & 15)
-  // lands at sm[256 q + 16 fi + fj].
-  for (int w = 0; w < kWaves; ++w) {
-    if (wave == w) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int e = kPairs * (3 * i + j) + kTF * ((lane >> 4) + 4 * r) + (lane & 15);
-            sm[e] = w == 0 ? acc[i][j][r] : sm[e] + acc[i][j][r];
-          }
-    }
-    __syncthreads();
-  }
+  // ---- the four waves' accumulators, summed in wave order: entry
+  // q = 3 ci + cj of the pair (fi = row, fj = col) lands at sm[256 q + 16 fi + fj]
+  wave_sum_3x3(acc, sm, lane, wave,
+               [](int i, int j, int row, int col) { return kPairs * (3 * i + j) + kTF * row + col; });
 
   if (direct) {
     double A[9];
@@ -419,23 +311,6 @@ __global__ __launch_bounds__(kBlock) void k_pw_fold(const double *__restrict__ w
     A[q] = s;
   }
   pair_epilogue(A, I, J, n_frames, g, superpose, w_total, cutoff, out, ld, sd);
-}
-
-// The LDS a kernel declares against the device's limit per workgroup, before
-// its first launch (a kernel over the limit would fail at launch with a less
-// helpful message).
-int lds_guard(const void *kernel, const char *name) {
-  hipFuncAttributes at;
-  hipError_t e = hipFuncGetAttributes(&at, kernel);
-  if (e != hipSuccess) return fail(RMSF_EHIP, std::string(name) + ": hipFuncGetAttributes: " + hipGetErrorString(e));
-  int dev = 0, limit = 0;
-  e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
-  if (e != hipSuccess) return fail(RMSF_EHIP, std::string(name) + ": device LDS limit: " + hipGetErrorString(e));
-  if (at.sharedSizeBytes > (size_t)limit)
-    return fail(RMSF_EINVAL, std::string(name) + ": the kernel declares " + std::to_string(at.sharedSizeBytes) +
-                                 " bytes of LDS, the device allows " + std::to_string(limit) + " a workgroup");
-  return RMSF_OK;
 }
 
 }  // namespace
@@ -480,13 +355,10 @@ RMSF_EXPORT int rmsf_pairwise_rmsd(const float *d_xyz, int64_t fstride, int64_t 
   const int direct = pl.n_ks == 1;
   double *work = static_cast<double *>(d_work);
   const dim3 grid((unsigned)pl.n_pairs, (unsigned)pl.n_ks), block(kBlock);
-#define PW_LAUNCH(G_, W_)                                                                                          \
-  do {                                                                                                             \
-    if (int rc = lds_guard(reinterpret_cast<const void *>(k_pw_tiles<G_, W_>), "rmsf_pairwise_rmsd")) return rc;   \
-    hipLaunchKernelGGL((k_pw_tiles<G_, W_>), grid, block, 0, S(stream), d_xyz, fstride, n_frames, n_sel, d_sel,    \
-                       d_weights, d_centre, d_g, superpose, w_total, cutoff, d_out, ld, work, pl.n_tiles,          \
-                       pl.n_pairs, pl.ks_atoms, direct);                                                           \
-  } while (0)
+#define PW_LAUNCH(G_, W_)                                                                                     \
+  hipLaunchKernelGGL((k_pw_tiles<G_, W_>), grid, block, 0, S(stream), d_xyz, fstride, n_frames, n_sel, d_sel, \
+                     d_weights, d_centre, d_g, superpose, w_total, cutoff, d_out, ld, work, pl.n_tiles,       \
+                     pl.n_pairs, pl.ks_atoms, direct)
   const bool gt = d_sel != nullptr, wt = d_weights != nullptr;
   if (gt && wt) PW_LAUNCH(true, true);
   else if (gt) PW_LAUNCH(true, false);
@@ -495,7 +367,6 @@ RMSF_EXPORT int rmsf_pairwise_rmsd(const float *d_xyz, int64_t fstride, int64_t 
 #undef PW_LAUNCH
   if (int rc = after_launch("k_pw_tiles")) return rc;
   if (!direct) {
-    if (int rc = lds_guard(reinterpret_cast<const void *>(k_pw_fold), "rmsf_pairwise_rmsd")) return rc;
     hipLaunchKernelGGL(k_pw_fold, dim3((unsigned)pl.n_pairs), block, 0, S(stream), work, n_frames, pl.n_tiles,
                        pl.n_pairs, pl.n_ks, d_g, superpose, w_total, cutoff, d_out, ld);
     if (int rc = after_launch("k_pw_fold")) return rc;

@@ -23,33 +23,14 @@
 //   * k_proj_fold   the split-K partials, summed in coordinate-range order.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
-#include <string>
 
-#include "rmsf_hip.h"
+#include "dense_f64.h"
 #include "rmsf_device.h"
-
-#define RMSF_EXPORT __attribute__((visibility("default")))
-
-extern "C" int rmsf_internal_set_error(int code, const char *msg);
+#include "rmsf_host.h"
 
 namespace {
 
-int fail(int code, const std::string &m) { return rmsf_internal_set_error(code, m.c_str()); }
-
-int after_launch(const char *what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(RMSF_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return RMSF_OK;
-}
-
-inline hipStream_t S(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
-
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kXform = RMSF_XFORM_DOUBLES;
-constexpr int kRec = 12;                   // doubles of a transform record apply_xform reads
 constexpr int kTF = 16;                    // frames a workgroup: the MFMA's M side
 constexpr int kTN = 16;                    // components an N tile
 constexpr int kMaxNT = 3;                  // N tiles a workgroup: a panel of 48 components
@@ -68,8 +49,8 @@ constexpr int64_t kMinStages = 16;         // no coordinate range under 512 atom
 static_assert(kBlock == kTF * kTA, "one (atom, frame) per thread and pass");
 static_assert(kKC % (4 * kWaves) == 0, "whole k-steps a wave");
 static_assert(2 * kKC * kLd >= kWaves * kTF * kPanel, "the waves' results fit the staging buffers");
+static_assert(sizeof(double) * (2 * kKC * kLd + kTF * kRec) <= kLdsLimit, "sm and sxf fit");
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef float f32x3 __attribute__((ext_vector_type(3)));
 
 // The barrier between a stage's LDS stores and its LDS reads: every wave
@@ -94,10 +75,9 @@ ProjPlan proj_plan(int64_t n_frames, int64_t n_sel, int64_t n_comp) {
   p.n_nt = (int)std::min<int64_t>(kMaxNT, (n_comp + kTN - 1) / kTN);
   const int64_t stages = std::max<int64_t>(1, (n_sel + kKA - 1) / kKA);
   const int64_t base = std::max<int64_t>(1, p.n_ft * p.n_pan);
-  int64_t ks = std::max<int64_t>(1, std::min<int64_t>(stages / kMinStages, kTargetGroups / base));
-  const int64_t per = (stages + ks - 1) / ks;
-  p.n_ks = (stages + per - 1) / per;
-  p.ks_atoms = per * kKA;
+  const SplitK k = split_k(stages, base, kTargetGroups, kMinStages);
+  p.n_ks = k.n_ks;
+  p.ks_atoms = k.per * kKA;
   return p;
 }
 

@@ -1,13 +1,19 @@
 // rmsf_device.h -- device math shared by the HIP translation units
-// (rmsf_kernels.hip: the two-pass superpose/accumulate kernels; fused.hip:
-// the single-read fused sweep): the f32-faithful transform of RMSF.py:99-101
-// / 133-135 and the QCP solve of qcprot (RMSF.py:43-51).  Both kernels call
-// exactly this code, so a frame's rotation and its transformed coordinates
-// come out of the same instruction sequence on either path.
+// (rmsf_kernels.hip: the superpose/accumulate kernels; covariance.hip,
+// pca_project.hip: the dense sweeps over aligned frames; pairwise.hip: the
+// all-pairs RMSD): the f32-faithful transform of RMSF.py:99-101 / 133-135 and
+// the QCP solve of qcprot (RMSF.py:43-51).  Every kernel calls exactly this
+// code, so a frame's rotation, its transformed coordinates and a pair's
+// lambda come out of the same instruction sequence on every path.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+
+#include "rmsf_hip.h"
+
+constexpr int kXform = RMSF_XFORM_DOUBLES;  // doubles of a frame's transform record
+constexpr int kRec = 12;                    // ... of which apply_xform reads the first: R (9), the mobile COM (3)
 
 // ---------------------------------------------------------------------------
 // f32-faithful superposition transform of RMSF.py:99-101 / 133-135.
@@ -37,8 +43,10 @@ __device__ __forceinline__ void apply_xform(float &x, float &y, float &z, const 
 // 31:1561, 2010), as used by MDAnalysis.lib.qcprot (RMSF.py:48).  A is the
 // row-major inner product sum_i mob_i[a] ref_i[b]; rot is applied as x @ rot.
 // SURVEY.md Appendix A.2-A.3 gives the exact sequence followed here.
-__host__ __device__ inline void qcp_solve(const double *A, double E0, double len, double *rot,
-                                          double *rmsd) {
+//
+// The largest root of the QCP quartic: the coefficients, Newton's iteration
+// from lambda = E0 (an upper bound) and its stopping rule.
+__host__ __device__ inline double qcp_lambda(const double *A, double E0) {
   const double Sxx = A[0], Sxy = A[1], Sxz = A[2];
   const double Syx = A[3], Syy = A[4], Syz = A[5];
   const double Szx = A[6], Szy = A[7], Szz = A[8];
@@ -71,7 +79,6 @@ __host__ __device__ inline void qcp_solve(const double *A, double E0, double len
       (+(SxypSyx) * (SyzmSzy) + (SxzmSzx) * (SxxmSyy - Szz)) *
           (-(SxymSyx) * (SyzpSzy) + (SxzmSzx) * (SxxpSyy - Szz));
 
-  // Newton-Raphson on the quartic, from lambda = E0 (upper bound).
   double l = E0;
   for (int i = 0; i < 50; ++i) {
     const double old = l;
@@ -82,6 +89,21 @@ __host__ __device__ inline void qcp_solve(const double *A, double E0, double len
     l -= delta;
     if (fabs(l - old) < fabs(1e-11 * l)) break;
   }
+  return l;
+}
+
+// The rotation and the RMSD from that root; the sums and differences of A's
+// entries are the adjoint's, the same adds as in qcp_lambda.
+__host__ __device__ inline void qcp_solve(const double *A, double E0, double len, double *rot,
+                                          double *rmsd) {
+  const double Sxx = A[0], Sxy = A[1], Sxz = A[2];
+  const double Syx = A[3], Syy = A[4], Syz = A[5];
+  const double Szx = A[6], Szy = A[7], Szz = A[8];
+
+  const double SxzpSzx = Sxz + Szx, SyzpSzy = Syz + Szy, SxypSyx = Sxy + Syx;
+  const double SyzmSzy = Syz - Szy, SxzmSzx = Sxz - Szx, SxymSyx = Sxy - Syx;
+  const double SxxpSyy = Sxx + Syy, SxxmSyy = Sxx - Syy;
+  const double l = qcp_lambda(A, E0);
   *rmsd = sqrt(fabs(2.0 * (E0 - l) / len));
 
   const double a11 = SxxpSyy + Szz - l, a12 = SyzmSzy, a13 = -SxzmSzx, a14 = SxymSyx;

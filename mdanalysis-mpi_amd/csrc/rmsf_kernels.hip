@@ -65,7 +65,6 @@ int after_launch(const char *what) {
 inline hipStream_t S(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
 
 constexpr int kBlock = 256;
-constexpr int kXform = RMSF_XFORM_DOUBLES;
 constexpr int kStats = 16;       // doubles per (frame, chunk) partial
 constexpr int64_t kAccumBlocks = 3584;       // target workgroups, k_welford_flat
 constexpr int64_t kAccumBlocksAtom = 4608;   // target workgroups, k_accum_atoms

@@ -22,20 +22,15 @@
 #include <vector>
 
 #include "rmsf_hip.h"
+#include "rmsf_host.h"
 #include "host_affinity.h"
 
-#define RMSF_EXPORT __attribute__((visibility("default")))
-
-// error reporting shared with rmsf_kernels.hip through this small hook
-extern "C" int rmsf_internal_set_error(int code, const char *msg);
 extern "C" int rmsf_internal_xtc_decode(const rmsf_xtc *x, int64_t f0, int64_t n, int64_t step, const int32_t *sel,
                                         int64_t n_sel, float *out, int64_t out_stride, int n_threads);
 extern "C" int64_t rmsf_internal_xtc_natoms(const rmsf_xtc *x);
 extern "C" int64_t rmsf_internal_xtc_nframes(const rmsf_xtc *x);
 
 namespace {
-
-int fail(int code, const std::string &m) { return rmsf_internal_set_error(code, m.c_str()); }
 
 #define ST_HIP(expr)                                                                              \
   do {                                                                                            \

@@ -30,15 +30,10 @@
 #include <vector>
 
 #include "rmsf_hip.h"
+#include "rmsf_host.h"
 #include "xtc_internal.h"
 
-#define RMSF_EXPORT __attribute__((visibility("default")))
-
-extern "C" int rmsf_internal_set_error(int code, const char *msg);
-
 namespace {
-
-int fail(int code, const std::string &m) { return rmsf_internal_set_error(code, m.c_str()); }
 
 constexpr int kMagic = 1995;
 constexpr int magicints[] = {

@@ -47,6 +47,78 @@ def test_workspace_bytes_and_argument_checks_on_the_host():
     assert lib.rmsf_covariance_finish(one, 3, one, 3, 0, None) == _lib.RMSF_EEMPTY
 
 
+# rmsf_covariance_workspace_bytes(n_sel, n_frames), recorded before the plan
+# arithmetic moved into csrc/dense_f64.h: the GPU tests' and
+# tools/bench_covariance.py's shapes, then the tile edges x the stage edges.
+PLAN_BYTES = [
+    (1, 1, 0), (5, 3, 0), (16, 4, 0), (17, 5, 0), (214, 67, 5822208), (341, 300, 9343488), (341, 128, 9343488),
+    (341, 44, 9343488), (500, 40, 0), (214, 300, 7762944), (214, 20000, 7762944), (3341, 4000, 0), (1, 31, 0),
+    (1, 32, 0), (1, 33, 37632), (1, 511, 301056), (1, 512, 301056), (1, 513, 319872), (1, 5000, 2954112),
+    (1, 100000, 8410752), (15, 1, 0), (15, 31, 0), (15, 32, 0), (15, 33, 37632), (15, 511, 301056), (15, 512, 301056),
+    (15, 513, 319872), (15, 5000, 2954112), (15, 100000, 8410752), (16, 1, 0), (16, 31, 0), (16, 32, 0),
+    (16, 33, 37632), (16, 511, 301056), (16, 512, 301056), (16, 513, 319872), (16, 5000, 2954112),
+    (16, 100000, 8410752), (17, 1, 0), (17, 31, 0), (17, 32, 0), (17, 33, 112128), (17, 511, 897024),
+    (17, 512, 897024), (17, 513, 953088), (17, 5000, 8802048), (17, 100000, 9250560), (31, 1, 0), (31, 31, 0),
+    (31, 32, 0), (31, 33, 112128), (31, 511, 897024), (31, 512, 897024), (31, 513, 953088), (31, 5000, 8802048),
+    (31, 100000, 9250560), (32, 1, 0), (32, 31, 0), (32, 32, 0), (32, 33, 112128), (32, 511, 897024),
+    (32, 512, 897024), (32, 513, 953088), (32, 5000, 8802048), (32, 100000, 9250560), (33, 1, 0), (33, 31, 0),
+    (33, 32, 0), (33, 33, 223488), (33, 511, 1787904), (33, 512, 1787904), (33, 513, 1899648), (33, 5000, 8827776),
+    (33, 100000, 9498240), (496, 1, 0), (496, 31, 0), (496, 32, 0), (496, 33, 0), (496, 511, 0), (496, 512, 0),
+    (496, 513, 0), (496, 5000, 0), (496, 100000, 0), (497, 1, 0), (497, 31, 0), (497, 32, 0), (497, 33, 0),
+    (497, 511, 0), (497, 512, 0), (497, 513, 0), (497, 5000, 0), (497, 100000, 0), (512, 1, 0), (512, 31, 0),
+    (512, 32, 0), (512, 33, 0), (512, 511, 0), (512, 512, 0), (512, 513, 0), (512, 5000, 0), (512, 100000, 0),
+    (513, 1, 0), (513, 31, 0), (513, 32, 0), (513, 33, 0), (513, 511, 0), (513, 512, 0), (513, 513, 0),
+    (513, 5000, 0), (513, 100000, 0),
+]
+
+
+def test_workspace_bytes_are_the_recorded_plan():
+    from rmsf_amd import _lib
+    wb = _lib.load().rmsf_covariance_workspace_bytes
+    assert [(n_sel, n_frames, wb(n_sel, n_frames)) for n_sel, n_frames, _ in PLAN_BYTES] == PLAN_BYTES
+
+
+def _pair_to_tiles():
+    from rmsf_amd import _lib
+    fn = _lib.load().rmsf_internal_pair_to_tiles
+    fn.restype = None
+    fn.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    i, j = ctypes.c_int64(), ctypes.c_int64()
+
+    def mapped(p, n_tiles):
+        i.value = j.value = -1
+        fn(p, n_tiles, ctypes.byref(i), ctypes.byref(j))
+        return i.value, j.value
+    return mapped
+
+
+@pytest.mark.parametrize("n_tiles", [1, 2, 3, 22, 209, 256])
+def test_pair_to_tiles_is_the_upper_triangle_in_row_order(n_tiles):
+    """The tile mapping of k_cov_tiles, k_cov_fold, k_pw_tiles and k_pw_fold
+    (csrc/dense_f64.h), on the host: a wrong (I, J) there is an out-of-bounds
+    store."""
+    mapped = _pair_to_tiles()
+    p = 0
+    for i in range(n_tiles):
+        for j in range(i, n_tiles):
+            assert mapped(p, n_tiles) == (i, j), p
+            p += 1
+    assert p == n_tiles * (n_tiles + 1) // 2
+
+
+def test_pair_to_tiles_at_the_largest_grid():
+    """65,535 tiles a side: the most that n_pairs <= INT32_MAX admits.  The
+    first and the last pair of every row, where the square root's rounding
+    would show."""
+    mapped = _pair_to_tiles()
+    n = 65535
+    assert n * (n + 1) // 2 <= 2 ** 31 - 1 < (n + 1) * (n + 2) // 2
+    for i in range(n):
+        first = i * n - i * (i - 1) // 2
+        assert mapped(first, n) == (i, i), i
+        assert mapped(first + n - i - 1, n) == (i, n - 1), i
+
+
 def _random_psd(n, seed):
     rng = np.random.default_rng(seed)
     a = rng.normal(size=(n, 2 * n)) * rng.uniform(0.1, 3.0, size=(n, 1))

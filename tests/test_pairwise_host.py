@@ -34,6 +34,37 @@ def test_workspace_bytes():
     assert wb(256, 100_000) > 0 and wb(256, 100_000) % (8 * 9 * 256 * 136) == 0
 
 
+# rmsf_pairwise_workspace_bytes(n_frames, n_sel), recorded before the plan
+# arithmetic moved into csrc/dense_f64.h: the GPU tests' and
+# tools/bench_pairwise.py's shapes, then the tile edges x the stage edges.
+PLAN_BYTES = [
+    (2, 3, 0), (15, 4, 0), (16, 17, 0), (17, 33, 110592), (33, 31, 0), (50, 214, 1290240), (5, 5000, 2893824),
+    (9, 31, 0), (9, 32, 0), (9, 33, 36864), (20, 31, 0), (11, 31, 0), (500, 40, 0), (4096, 214, 0), (4096, 3341, 0),
+    (256, 100000, 7520256), (1, 1, 0), (1, 31, 0), (1, 32, 0), (1, 33, 36864), (1, 511, 294912), (1, 512, 294912),
+    (1, 513, 313344), (1, 5000, 2893824), (1, 100000, 8239104), (15, 1, 0), (15, 31, 0), (15, 32, 0), (15, 33, 36864),
+    (15, 511, 294912), (15, 512, 294912), (15, 513, 313344), (15, 5000, 2893824), (15, 100000, 8239104), (16, 1, 0),
+    (16, 31, 0), (16, 32, 0), (16, 33, 36864), (16, 511, 294912), (16, 512, 294912), (16, 513, 313344),
+    (16, 5000, 2893824), (16, 100000, 8239104), (17, 1, 0), (17, 31, 0), (17, 32, 0), (17, 511, 884736),
+    (17, 512, 884736), (17, 513, 940032), (17, 5000, 8681472), (17, 100000, 9123840), (31, 1, 0), (31, 31, 0),
+    (31, 32, 0), (31, 33, 110592), (31, 511, 884736), (31, 512, 884736), (31, 513, 940032), (31, 5000, 8681472),
+    (31, 100000, 9123840), (32, 1, 0), (32, 31, 0), (32, 32, 0), (32, 33, 110592), (32, 511, 884736),
+    (32, 512, 884736), (32, 513, 940032), (32, 5000, 8681472), (32, 100000, 9123840), (33, 1, 0), (33, 32, 0),
+    (33, 33, 221184), (33, 511, 1769472), (33, 512, 1769472), (33, 513, 1880064), (33, 5000, 8736768),
+    (33, 100000, 9400320), (496, 1, 0), (496, 31, 0), (496, 32, 0), (496, 33, 0), (496, 511, 0), (496, 512, 0),
+    (496, 513, 0), (496, 5000, 0), (496, 100000, 0), (497, 1, 0), (497, 31, 0), (497, 32, 0), (497, 33, 0),
+    (497, 511, 0), (497, 512, 0), (497, 513, 0), (497, 5000, 0), (497, 100000, 0), (512, 1, 0), (512, 31, 0),
+    (512, 32, 0), (512, 33, 0), (512, 511, 0), (512, 512, 0), (512, 513, 0), (512, 5000, 0), (512, 100000, 0),
+    (513, 1, 0), (513, 31, 0), (513, 32, 0), (513, 33, 0), (513, 511, 0), (513, 512, 0), (513, 513, 0),
+    (513, 5000, 0), (513, 100000, 0),
+]
+
+
+def test_workspace_bytes_are_the_recorded_plan():
+    from rmsf_amd import _lib
+    wb = _lib.load().rmsf_pairwise_workspace_bytes
+    assert [(n_frames, n_sel, wb(n_frames, n_sel)) for n_frames, n_sel, _ in PLAN_BYTES] == PLAN_BYTES
+
+
 def test_argument_checks_come_before_any_launch():
     from rmsf_amd import _lib
     lib = _lib.load()

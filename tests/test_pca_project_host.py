@@ -35,6 +35,58 @@ def test_workspace_bytes_deterministic():
         assert [ws(*s) for s in shapes] == first
 
 
+# rmsf_pca_project_workspace_bytes(n_frames, n_sel, n_comp), recorded before
+# the plan arithmetic moved into csrc/dense_f64.h: the GPU tests' and
+# tools/bench_pca_project.py's shapes, then the tile edges x the stage edges
+# at 3 and 49 components (one panel, two).
+PLAN_BYTES = [
+    (1, 1, 1, 0), (3, 5, 2, 0), (16, 16, 16, 0), (17, 17, 17, 0), (33, 17, 51, 0), (67, 214, 10, 0), (300, 341, 7, 0),
+    (128, 341, 7, 0), (44, 341, 7, 0), (5, 5000, 3, 1080), (5, 17, 51, 0), (67, 214, 642, 0), (300, 341, 10, 0),
+    (20000, 214, 10, 0), (20000, 214, 48, 0), (4096, 3341, 10, 1310720), (4096, 3341, 48, 6291456),
+    (256, 100000, 10, 1310720), (256, 100000, 48, 6291456), (1, 1, 3, 0), (1, 1, 49, 0), (1, 31, 3, 0),
+    (1, 31, 49, 0), (1, 32, 3, 0), (1, 32, 49, 0), (1, 33, 3, 0), (1, 33, 49, 0), (1, 511, 3, 0), (1, 511, 49, 0),
+    (1, 512, 3, 0), (1, 512, 49, 0), (1, 513, 3, 0), (1, 513, 49, 0), (1, 5000, 3, 216), (1, 5000, 49, 3528),
+    (1, 100000, 3, 4416), (1, 100000, 49, 72128), (15, 1, 3, 0), (15, 1, 49, 0), (15, 31, 3, 0), (15, 31, 49, 0),
+    (15, 32, 3, 0), (15, 32, 49, 0), (15, 33, 3, 0), (15, 33, 49, 0), (15, 511, 3, 0), (15, 511, 49, 0),
+    (15, 512, 3, 0), (15, 512, 49, 0), (15, 513, 3, 0), (15, 513, 49, 0), (15, 5000, 3, 3240), (15, 5000, 49, 52920),
+    (15, 100000, 3, 66240), (15, 100000, 49, 1081920), (16, 1, 3, 0), (16, 1, 49, 0), (16, 31, 3, 0), (16, 31, 49, 0),
+    (16, 32, 3, 0), (16, 32, 49, 0), (16, 33, 3, 0), (16, 33, 49, 0), (16, 511, 3, 0), (16, 511, 49, 0),
+    (16, 512, 3, 0), (16, 512, 49, 0), (16, 513, 3, 0), (16, 513, 49, 0), (16, 5000, 3, 3456), (16, 5000, 49, 56448),
+    (16, 100000, 3, 70656), (16, 100000, 49, 1154048), (17, 1, 3, 0), (17, 1, 49, 0), (17, 31, 3, 0), (17, 31, 49, 0),
+    (17, 32, 3, 0), (17, 32, 49, 0), (17, 33, 3, 0), (17, 33, 49, 0), (17, 511, 3, 0), (17, 511, 49, 0),
+    (17, 512, 3, 0), (17, 512, 49, 0), (17, 513, 3, 0), (17, 513, 49, 0), (17, 5000, 3, 3672), (17, 5000, 49, 59976),
+    (17, 100000, 3, 75072), (17, 100000, 49, 1226176), (31, 1, 3, 0), (31, 1, 49, 0), (31, 31, 3, 0), (31, 31, 49, 0),
+    (31, 32, 3, 0), (31, 32, 49, 0), (31, 33, 3, 0), (31, 33, 49, 0), (31, 511, 3, 0), (31, 511, 49, 0),
+    (31, 512, 3, 0), (31, 512, 49, 0), (31, 513, 3, 0), (31, 513, 49, 0), (31, 5000, 3, 6696), (31, 5000, 49, 109368),
+    (31, 100000, 3, 136896), (31, 100000, 49, 2235968), (32, 1, 3, 0), (32, 1, 49, 0), (32, 31, 3, 0),
+    (32, 31, 49, 0), (32, 32, 3, 0), (32, 32, 49, 0), (32, 33, 3, 0), (32, 33, 49, 0), (32, 511, 3, 0),
+    (32, 511, 49, 0), (32, 512, 3, 0), (32, 512, 49, 0), (32, 513, 3, 0), (32, 513, 49, 0), (32, 5000, 3, 6912),
+    (32, 5000, 49, 112896), (32, 100000, 3, 141312), (32, 100000, 49, 2308096), (33, 1, 3, 0), (33, 1, 49, 0),
+    (33, 31, 3, 0), (33, 31, 49, 0), (33, 32, 3, 0), (33, 32, 49, 0), (33, 33, 3, 0), (33, 33, 49, 0),
+    (33, 511, 3, 0), (33, 511, 49, 0), (33, 512, 3, 0), (33, 512, 49, 0), (33, 513, 3, 0), (33, 513, 49, 0),
+    (33, 5000, 3, 7128), (33, 5000, 49, 116424), (33, 100000, 3, 145728), (33, 100000, 49, 2134440), (496, 1, 3, 0),
+    (496, 1, 49, 0), (496, 31, 3, 0), (496, 31, 49, 0), (496, 32, 3, 0), (496, 32, 49, 0), (496, 33, 3, 0),
+    (496, 33, 49, 0), (496, 511, 3, 0), (496, 511, 49, 0), (496, 512, 3, 0), (496, 512, 49, 0), (496, 513, 3, 0),
+    (496, 513, 49, 0), (496, 5000, 3, 107136), (496, 5000, 49, 1749888), (496, 100000, 3, 392832),
+    (496, 100000, 49, 3110912), (497, 1, 3, 0), (497, 1, 49, 0), (497, 31, 3, 0), (497, 31, 49, 0), (497, 32, 3, 0),
+    (497, 32, 49, 0), (497, 33, 3, 0), (497, 33, 49, 0), (497, 511, 3, 0), (497, 511, 49, 0), (497, 512, 3, 0),
+    (497, 512, 49, 0), (497, 513, 3, 0), (497, 513, 49, 0), (497, 5000, 3, 107352), (497, 5000, 49, 1753416),
+    (497, 100000, 3, 381696), (497, 100000, 49, 3117184), (512, 1, 3, 0), (512, 1, 49, 0), (512, 31, 3, 0),
+    (512, 31, 49, 0), (512, 32, 3, 0), (512, 32, 49, 0), (512, 33, 3, 0), (512, 33, 49, 0), (512, 511, 3, 0),
+    (512, 511, 49, 0), (512, 512, 3, 0), (512, 512, 49, 0), (512, 513, 3, 0), (512, 513, 49, 0),
+    (512, 5000, 3, 110592), (512, 5000, 49, 1806336), (512, 100000, 3, 393216), (512, 100000, 49, 3211264),
+    (513, 1, 3, 0), (513, 1, 49, 0), (513, 31, 3, 0), (513, 31, 49, 0), (513, 32, 3, 0), (513, 32, 49, 0),
+    (513, 33, 3, 0), (513, 33, 49, 0), (513, 511, 3, 0), (513, 511, 49, 0), (513, 512, 3, 0), (513, 512, 49, 0),
+    (513, 513, 3, 0), (513, 513, 49, 0), (513, 5000, 3, 110808), (513, 5000, 49, 1809864), (513, 100000, 3, 381672),
+    (513, 100000, 49, 3016440),
+]
+
+
+def test_workspace_bytes_are_the_recorded_plan():
+    ws = _lib().rmsf_pca_project_workspace_bytes
+    assert [(f, n, k, ws(f, n, k)) for f, n, k, _ in PLAN_BYTES] == PLAN_BYTES
+
+
 @pytest.mark.parametrize("i", [0, 1, 4])
 def test_cosine_content_of_a_cosine(i):
     from rmsf_amd import cosine_content

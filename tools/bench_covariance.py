@@ -20,49 +20,17 @@ import json
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mdanalysis-mpi_amd")]
+
+from bench_timing import spread, timed_events, timed_host  # noqa: E402  (beside this file)
 
 SHAPES = [  # name, atoms per frame, selected atoms, frames
     ("214_of_47681_x_20000", 47681, 214, 20000),
     ("214_x_20000_dense", 214, 214, 20000),
     ("3341_x_4000_dense", 3341, 3341, 4000),
 ]
-
-
-def spread(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "reps": len(ms)}
-
-
-def timed_events(fn, reps, before=None):
-    import torch
-    out = []
-    for i in range(reps + 2):  # two warm-up repetitions
-        if before is not None:
-            before()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        if i >= 2:
-            out.append(a.elapsed_time(b))
-    return out
-
-
-def timed_host(fn, reps):
-    import torch
-    out = []
-    for i in range(reps + 1):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if i >= 1:
-            out.append(1e3 * (time.perf_counter() - t))
-    return out
 
 
 def main(argv=None) -> int:

@@ -27,30 +27,14 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mdanalysis-mpi_amd")]
 
+from bench_timing import spread, timed_events  # noqa: E402  (beside this file)
+
 SHAPES = [  # name, atoms per frame, selected atoms, frames
     ("214_x_4096_dense", 214, 214, 4096),
     ("3341_x_4096_dense", 3341, 3341, 4096),
     ("214_of_47681_x_4096", 47681, 214, 4096),
     ("100000_x_256_splitk", 100_000, 100_000, 256),
 ]
-
-
-def spread(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "reps": len(ms)}
-
-
-def timed_events(fn, reps):
-    import torch
-    out = []
-    for i in range(reps + 2):  # two warm-up repetitions
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        if i >= 2:
-            out.append(a.elapsed_time(b))
-    return out
 
 
 def main(argv=None) -> int:

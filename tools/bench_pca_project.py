@@ -27,10 +27,11 @@ import json
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mdanalysis-mpi_amd")]
+
+from bench_timing import spread, timed_host  # noqa: E402  (beside this file)
 
 SHAPES = [  # name, atoms per frame, selected atoms, frames, aligned PCA feasible
     ("214_x_20000_dense", 214, 214, 20_000, True),
@@ -40,10 +41,6 @@ SHAPES = [  # name, atoms per frame, selected atoms, frames, aligned PCA feasibl
 ]
 COMPONENTS = (10, 48)
 HBM_PEAK_TBS = 8.0
-
-
-def spread(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "reps": len(ms)}
 
 
 def timed_pair(fns, reps, inner):
@@ -60,19 +57,6 @@ def timed_pair(fns, reps, inner):
             torch.cuda.synchronize()
             if i >= 2:
                 out[j].append(a.elapsed_time(b) / inner)
-    return out
-
-
-def timed_host(fn, reps):
-    import torch
-    out = []
-    for i in range(reps + 1):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if i >= 1:
-            out.append((time.perf_counter() - t0) * 1e3)
     return out
 
 
