@@ -569,6 +569,53 @@ int rmsf_pca_project(const float *d_xyz, int64_t frame_stride,
                      int64_t n_comp, double *d_out, int64_t ldo, void *d_work,
                      size_t work_bytes, void *stream);
 
+/* ---- block products of a device-side eigen-solver (PCA(solver="device")) ---
+ * The three products of a blocked subspace iteration with Rayleigh-Ritz on a
+ * symmetric f64 matrix that stays in HBM (csrc/eigen_block.hip; the driver is
+ * rmsf_amd/eigen.py).  A block is a tall, skinny f64 matrix of n rows and at
+ * most 48 columns; every leading dimension is in doubles, and the columns of
+ * a row past the block's width are neither read nor written.
+ * rmsf_symm_block:  d_y[r * ldy + c] = sum_k d_m[r * ldm + k] d_q[k * ldq + c]
+ *   for r < n, c < n_cols <= 48: Y = M Q on the f64 matrix cores
+ *   (v_mfma_f64_16x16x4_f64), M read once (8 n^2 bytes).
+ *   PRECONDITION: d_m [n][ldm >= n] is symmetric in its bits, d_m[i][j] ==
+ *   d_m[j][i] -- the kernel reads M[k][r] where the formula has M[r][k].
+ *   rmsf_covariance_finish writes such a matrix; an element-wise division of
+ *   it keeps the property.  Work is cut into (48 rows of Y, range of k)
+ *   workgroups; with more than one range the partials go to d_work
+ *   (rmsf_symm_block_workspace_bytes() bytes, 0 when none is needed and
+ *   d_work may be NULL) and are summed in range order by a second launch.
+ * rmsf_block_gram:  d_g[i * ldg + j] = sum_r d_a[r * lda + i] d_b[r * ldb + j]
+ *   for i < na <= 48, j < nb <= 48: G = A^T B, contracted over the n rows on
+ *   the matrix cores; the rows are cut into ranges over the workgroups, whose
+ *   partials go to d_work (rmsf_block_gram_workspace_bytes() bytes, as above)
+ *   and are summed in range order.  d_a == d_b is allowed.
+ * rmsf_block_update:  d_c[r * ldc + c] = alpha d_a[r * lda + c]
+ *   + sum_j d_b[r * ldb + j] d_t[j * ldt + c]  for r < n, c < nc <= 48, j < nb
+ *   <= 48: C = alpha A + B T with the small matrix T [nb][ldt >= nc] in HBM,
+ *   the nb products summed in order of j.  d_a NULL: C = B T.  d_c may be
+ *   d_a; it must not be d_b.
+ * No floating-point atomics; every plan is a function of the shape alone
+ * (n and the column counts): the same bits for the same inputs.  The
+ * *_workspace_bytes functions are host-only arithmetic (no device).  Bad
+ * arguments (a NULL pointer other than d_a and an unneeded d_work, a size
+ * < 1, a leading dimension smaller than the width it strides, more than 48
+ * columns, a workspace too small): RMSF_EINVAL.                              */
+size_t rmsf_symm_block_workspace_bytes(int64_t n, int64_t n_cols);
+int rmsf_symm_block(const double *d_m, int64_t ldm, int64_t n,
+                    const double *d_q, int64_t ldq, int64_t n_cols,
+                    double *d_y, int64_t ldy, void *d_work, size_t work_bytes,
+                    void *stream);
+size_t rmsf_block_gram_workspace_bytes(int64_t n, int64_t na, int64_t nb);
+int rmsf_block_gram(const double *d_a, int64_t lda, int64_t na,
+                    const double *d_b, int64_t ldb, int64_t nb, int64_t n,
+                    double *d_g, int64_t ldg, void *d_work, size_t work_bytes,
+                    void *stream);
+int rmsf_block_update(double alpha, const double *d_a, int64_t lda,
+                      const double *d_b, int64_t ldb, int64_t nb,
+                      const double *d_t, int64_t ldt, int64_t n, int64_t nc,
+                      double *d_c, int64_t ldc, void *stream);
+
 /* ---- all-pairs RMSD matrix (MDAnalysis.analysis.diffusionmap.DistanceMatrix)
  * The n_frames x n_frames matrix of RMSDs between every pair of frames of a
  * batch read at a constant frame_stride, on the f64 matrix cores

@@ -1,5 +1,5 @@
-// dense_f64.h -- what the three dense f64 MFMA contractions (covariance.hip,
-// pairwise.hip, pca_project.hip) have in common: the workgroup's shape, the
+// dense_f64.h -- what the dense f64 MFMA contractions (covariance.hip,
+// pairwise.hip, pca_project.hip, eigen_block.hip) have in common: the workgroup's shape, the
 // 3 x 3 block of v_mfma_f64_16x16x4_f64 and its wave-order sum, the split-K
 // plan and the upper block triangle's pair index.  Staging, pipelining and
 // the fold kernels differ for reasons DESIGN.md records and stay in each file.
@@ -44,16 +44,17 @@ __device__ __forceinline__ void mfma_3x3(f64x4 (&acc)[3][3], double a0, double a
 // a lane only meets its own.  at(i, j, row, col) is where element (row, col)
 // of MFMA tile (i, j) lands in sm.  lane and wave are the kernel's own values
 // (recomputed here from threadIdx, the compiler no longer pairs the LDS
-// accesses).  Called by every thread; ends on a barrier.
-template <int N, class At>
-__device__ __forceinline__ void wave_sum_3x3(const f64x4 (&acc)[3][3], double (&sm)[N], int lane, int wave,
+// accesses).  Called by every thread; ends on a barrier.  NJ: the column
+// tiles held (3, or fewer where a kernel is built for narrower panels).
+template <int N, int NJ, class At>
+__device__ __forceinline__ void wave_sum_3x3(const f64x4 (&acc)[3][NJ], double (&sm)[N], int lane, int wave,
                                              At at) {
   for (int w = 0; w < kWaves; ++w) {
     if (wave == w) {
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j)
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int e = at(i, j, (lane >> 4) + 4 * r, lane & 15);

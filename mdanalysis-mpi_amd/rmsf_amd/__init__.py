@@ -9,7 +9,8 @@ Public surface (mirrors the reference's names):
   * ``PCA`` / ``pca_from_comoment`` -- the modes of the positional covariance
     (``RMSF(..., covariance=True)``), named as MDAnalysis.analysis.pca.PCA names them;
     ``PCA.transform`` projects a trajectory on them on the device, ``cosine_content``
-    measures such a projection's convergence
+    measures such a projection's convergence; ``PCA(solver="device")`` finds the first modes
+    on the device (``rmsf_amd.eigen.top_eigenpairs``) and raises ``PCAConvergenceError`` when it cannot
   * ``DistanceMatrix`` / ``DiffusionMap`` -- the all-pairs RMSD matrix of the frames and
     its diffusion map, named as MDAnalysis.analysis.diffusionmap names them
 """
@@ -18,6 +19,7 @@ from .parallel import blocks
 from .qcprot import CalcRMSDRotationalMatrix, get_rotation_matrix
 from .moments import second_order_moments
 from .rms import RMSF, Results
+from .eigen import PCAConvergenceError
 from .pca import PCA, cosine_content, pca_from_comoment
 from .distances import DiffusionMap, DistanceMatrix
 
@@ -27,6 +29,7 @@ __all__ = [
     "PCA",
     "pca_from_comoment",
     "cosine_content",
+    "PCAConvergenceError",
     "DistanceMatrix",
     "DiffusionMap",
     "blocks",

@@ -436,6 +436,52 @@ class Engine:
              mean.data_ptr(), comp.data_ptr(), comp.stride(0), n_comp, out.data_ptr(), out.stride(0), _ptr(work),
              0 if work is None else work.numel() * work.element_size(), self.stream)
 
+    # -- block products of the device eigen-solver (csrc/eigen_block.hip) -------
+    @staticmethod
+    def _is_block(t: torch.Tensor, rows: int, cols: int) -> bool:
+        return (t.dtype == F64 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= rows and t.shape[1] >= cols
+                and (t.shape[0] == 1 or t.stride(0) >= t.shape[1]))
+
+    def symm_block_workspace_bytes(self, n: int, n_cols: int) -> int:
+        return int(self.lib.rmsf_symm_block_workspace_bytes(n, n_cols))
+
+    def symm_block(self, m: torch.Tensor, n: int, q: torch.Tensor, n_cols: int, y: torch.Tensor,
+                   work: torch.Tensor | None = None) -> None:
+        """y[:n, :n_cols] = m[:n, :n] @ q[:n, :n_cols] on the f64 matrix cores
+        (rmsf_symm_block).  ``m`` must be symmetric in its bits (what
+        covariance_finish writes).  Rows of any of the three may be wider;
+        the other columns are neither read nor written.  ``work``: f64
+        scratch of at least symm_block_workspace_bytes(n, n_cols) bytes
+        (None when 0)."""
+        if not (self._is_block(m, n, n) and self._is_block(q, n, n_cols) and self._is_block(y, n, n_cols)):
+            raise ValueError("symm_block: buffer sizes")
+        call("rmsf_symm_block", m.data_ptr(), m.stride(0), n, q.data_ptr(), q.stride(0), n_cols, y.data_ptr(),
+             y.stride(0), _ptr(work), 0 if work is None else work.numel() * work.element_size(), self.stream)
+
+    def block_gram_workspace_bytes(self, n: int, na: int, nb: int) -> int:
+        return int(self.lib.rmsf_block_gram_workspace_bytes(n, na, nb))
+
+    def block_gram(self, a: torch.Tensor, na: int, b: torch.Tensor, nb: int, n: int, g: torch.Tensor,
+                   work: torch.Tensor | None = None) -> None:
+        """g[:na, :nb] = a[:n, :na].T @ b[:n, :nb] (rmsf_block_gram).
+        ``work``: f64 scratch of at least block_gram_workspace_bytes(n, na,
+        nb) bytes (None when 0)."""
+        if not (self._is_block(a, n, na) and self._is_block(b, n, nb) and self._is_block(g, na, nb)):
+            raise ValueError("block_gram: buffer sizes")
+        call("rmsf_block_gram", a.data_ptr(), a.stride(0), na, b.data_ptr(), b.stride(0), nb, n, g.data_ptr(),
+             g.stride(0), _ptr(work), 0 if work is None else work.numel() * work.element_size(), self.stream)
+
+    def block_update(self, alpha: float, a: torch.Tensor | None, b: torch.Tensor, nb: int, t: torch.Tensor, n: int,
+                     nc: int, c: torch.Tensor) -> None:
+        """c[:n, :nc] = alpha * a[:n, :nc] + b[:n, :nb] @ t[:nb, :nc], or
+        b @ t alone when ``a`` is None (rmsf_block_update).  ``c`` may be
+        ``a``; it must not be ``b``."""
+        if not (self._is_block(b, n, nb) and self._is_block(t, nb, nc) and self._is_block(c, n, nc)
+                and (a is None or self._is_block(a, n, nc))):
+            raise ValueError("block_update: buffer sizes")
+        call("rmsf_block_update", float(alpha), _ptr(a), 0 if a is None else a.stride(0), b.data_ptr(), b.stride(0),
+             nb, t.data_ptr(), t.stride(0), n, nc, c.data_ptr(), c.stride(0), self.stream)
+
     # -- all-pairs RMSD matrix (csrc/pairwise.hip) ----------------------------
     def pairwise_centres(self, xyz_ptr: int, fstride: int, n_frames: int, n_sel: int, sel, weights,
                          per_frame: bool = True):

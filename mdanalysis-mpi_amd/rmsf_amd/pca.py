@@ -6,7 +6,9 @@ also the preamble of ``pca.PCA``: the covariance of the aligned coordinates,
 of which the RMSF is the diagonal.  ``RMSF(..., covariance=True)`` forms that
 matrix on the device (csrc/covariance.hip, the f64 matrix cores) from the
 very coordinates the Welford sweep reads; the eigen-decomposition of the
-[3n, 3n] f64 matrix is ``numpy.linalg.eigh`` on the host.
+[3n, 3n] f64 matrix is ``numpy.linalg.eigh`` on the host, or, with
+``solver="device"``, the first modes by subspace iteration on the matrix where
+it lies (rmsf_amd/eigen.py over csrc/eigen_block.hip).
 
 ``PCA.transform()`` projects a trajectory on the components, on the device
 (csrc/pca_project.hip, the f64 matrix cores again): every frame is superposed
@@ -23,6 +25,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .eigen import MAX_COMPONENTS, PCAConvergenceError
 from .rms import RMSF, Results
 
 
@@ -130,17 +133,81 @@ class PCA:
 
     ``transform()`` then gives the projection of the trajectory (or of
     another one) on the components, f64 [n_frames, k].
+
+    ``solver="host"`` (the default) is ``numpy.linalg.eigh`` of the whole
+    matrix on the host.  ``solver="device"`` keeps the matrix in HBM and finds
+    the first ``n_components`` (required, 1..40) modes there by blocked
+    subspace iteration (``rmsf_amd.eigen.top_eigenpairs``; ``tol``,
+    ``max_iter`` and ``seed`` are its keywords).  Then ``results.covariance``
+    is the HBM ``torch.Tensor`` [3n, 3n] -- ``.cpu()`` is the caller's call --
+    while ``results.p_components`` and ``results.variance`` are host numpy as
+    with ``"host"`` (each component's largest entry positive),
+    ``results.cumulated_variance`` divides by the trace of the device matrix,
+    and ``results.solver_info`` is the solver's record (``n_iter``,
+    ``residuals``, ``rank``, ``block``, ``converged``).  A matrix with fewer
+    than ``n_components`` significant directions (a one-frame run) or an
+    iteration that does not converge raises ``PCAConvergenceError``.  Every
+    rank that holds the matrix runs the same deterministic solve.
     """
 
     def __init__(self, atomgroup, select=None, align="average", n_components: int | None = None, ddof: int = 1,
-                 **rmsf_kwargs):
+                 solver: str = "host", tol: float = 1e-10, max_iter: int = 300, seed: int = 0, **rmsf_kwargs):
+        if solver not in ("host", "device"):
+            raise ValueError(f'solver must be "host" or "device", got {solver!r}')
+        if solver == "device":
+            if n_components is None:
+                raise ValueError('solver="device" computes the first n_components modes: give n_components (a full '
+                                 'decomposition is solver="host"\'s job)')
+            if not 1 <= int(n_components) <= MAX_COMPONENTS:
+                raise ValueError(f'solver="device" computes 1..{MAX_COMPONENTS} components, got {n_components}; use '
+                                 'solver="host" for more')
         rmsf_kwargs.pop("covariance", None)
         self.n_components = n_components
         self.ddof = int(ddof)
+        self.solver, self.tol, self.max_iter, self.seed = solver, float(tol), int(max_iter), int(seed)
         self._rmsf = RMSF(atomgroup, select=select, align=align, covariance=True, **rmsf_kwargs)
+        self._rmsf._comoment_stays_in_hbm = solver == "device"
         self.results = Results()
 
+    def _run_device(self, start, stop, step, frames, **kwargs):
+        """``run()`` with ``solver="device"``: the finished co-moment stays
+        in HBM, is divided in place and handed to ``top_eigenpairs``."""
+        from .eigen import block_width, top_eigenpairs
+        from .engine import Engine
+
+        rm = self._rmsf
+        r = rm.run(start, stop, step, frames=frames, **kwargs).results
+        out = self.results
+        out.n_frames = r.n_frames
+        out.mean, out.rmsf = r.mean, r.rmsf
+        cov, rm._comoment_hbm = rm._comoment_hbm, None
+        if cov is None:  # a non-root rank of a reduce-to-root merge
+            out.covariance = out.p_components = out.variance = out.cumulated_variance = out.solver_info = None
+            return self
+        k = int(self.n_components)
+        if r.n_frames - self.ddof <= 0:  # one frame: the co-moment is exactly zero and there is nothing to divide by
+            info = {"n_iter": 0, "residuals": np.full(k, np.inf), "rank": 0, "block": 0, "converged": False}
+            out.solver_info = info
+            raise PCAConvergenceError(f"asked for {k} components, the matrix has rank 0: {r.n_frames} frame(s) with "
+                                      f"ddof = {self.ddof} leave no covariance", info)
+        block_width(cov.shape[0], k)  # ValueError for k > 3n, before any launch
+        import torch
+
+        eng = Engine(cov.device)
+        with torch.cuda.device(eng.device):
+            flat = cov.view(-1)
+            eng.divide(flat, float(r.n_frames - self.ddof), flat)  # x / d element by element, in place
+            out.covariance = cov
+            trace = float(cov.diagonal().cpu().numpy().sum())
+            out.variance, out.p_components, out.solver_info = top_eigenpairs(
+                cov, k, tol=self.tol, max_iter=self.max_iter, seed=self.seed)
+        out.cumulated_variance = np.cumsum(out.variance) / trace
+        self.n_frames = r.n_frames
+        return self
+
     def run(self, start=None, stop=None, step=None, frames=None, **kwargs):
+        if self.solver == "device":
+            return self._run_device(start, stop, step, frames, **kwargs)
         r = self._rmsf.run(start, stop, step, frames=frames, **kwargs).results
         out = self.results
         out.n_frames = r.n_frames

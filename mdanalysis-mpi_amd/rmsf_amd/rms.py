@@ -188,6 +188,8 @@ class RMSF:
         self.results = Results()
         self._source = None
         self._last_run = None
+        self._comoment_stays_in_hbm = False  # private: set by PCA(solver="device")
+        self._comoment_hbm = None
 
     # MDAnalysis AnalysisBase compatible signature
     def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
@@ -243,7 +245,11 @@ class RMSF:
                 r.transforms = res.transforms.cpu().numpy()
             if res.transforms_sweep1 is not None:
                 r.transforms_sweep1 = res.transforms_sweep1.cpu().numpy()
-            if self.covariance:
+            if self.covariance and self._comoment_stays_in_hbm:
+                # PCA(solver="device"): the caller takes the HBM tensor (None on a non-root rank); no copy
+                # to the host, no results.comoment
+                self._comoment_hbm = res.comoment
+            elif self.covariance:
                 r.comoment = host(res.comoment)
                 r.covariance = None if r.comoment is None else r.comoment / res.n_frames
             if "atom_slice" in res.extras:  # merge_scatter: this rank's slice of the statistics

@@ -62,11 +62,18 @@ def main(argv=None) -> int:
                          "frames on its components, f64 [F, K] (PCA.transform; one process only)")
     ap.add_argument("--n-components", type=int, default=None, metavar="K",
                     help="--pca-transform: the number of components (default: all 3n)")
+    ap.add_argument("--pca-solver", choices=["host", "device"], default="host",
+                    help="--pca-transform: numpy.linalg.eigh on the host, or the first --n-components (<= 40) modes "
+                         "by subspace iteration on the device, the matrix staying in HBM")
     a = ap.parse_args(argv)
     if a.pca_transform and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--pca-transform runs in one process (no torch.distributed launch)")
     if a.pca_transform and a.merge == "scatter":
         ap.error("--pca-transform needs --merge root or all")
+    if a.pca_solver == "device" and not a.pca_transform:
+        ap.error("--pca-solver device needs --pca-transform")
+    if a.pca_solver == "device" and a.n_components is None:
+        ap.error("--pca-solver device needs --n-components")
     if a.dist_matrix and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--dist-matrix runs in one process (no torch.distributed launch)")
     if a.covariance and a.merge == "scatter":
@@ -151,7 +158,8 @@ def main(argv=None) -> int:
     if a.pca_transform:
         from rmsf_amd import PCA
         pca_kw = {"select": dm_kw["select"], "masses": dm_kw["weights"]} if dm_kw else {}
-        pca = PCA(dm_input, align=align, ref_frame=a.ref_frame, n_components=a.n_components, **pca_kw).run()
+        pca = PCA(dm_input, align=align, ref_frame=a.ref_frame, n_components=a.n_components,
+                  solver=a.pca_solver, **pca_kw).run()
         proj = pca.transform()
         print(f"PCA projection of {proj.shape[0]} frames on {proj.shape[1]} components: the first holds "
               f"{pca.results.cumulated_variance[0]:.4f} of the variance", flush=True)
