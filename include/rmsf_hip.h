@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RMSF_ABI_VERSION 1
+#define RMSF_ABI_VERSION 2
 
 #define RMSF_OK 0
 #define RMSF_EINVAL (-1)   /* bad argument (shape, null pointer, size)      */
@@ -568,6 +568,45 @@ int rmsf_pca_project(const float *d_xyz, int64_t frame_stride,
                      const double *d_mean, const double *d_comp, int64_t ldc,
                      int64_t n_comp, double *d_out, int64_t ldo, void *d_work,
                      size_t work_bytes, void *stream);
+
+/* ---- PCA back-projection: the adjoint of the projection --------------------
+ * The product that contracts over the frames, [3 n_sel x n_frames] . [n_frames
+ * x n_cols] on the f64 matrix cores (csrc/pca_backproject.hip).  With
+ * rmsf_pca_project it is the matrix-free covariance product
+ * M Q = D^T (D Q) / (F - ddof) of PCA(solver="matrix_free"), which never
+ * forms the [3n, 3n] matrix.  Everything not stated here follows
+ * rmsf_pca_project: the coordinate index i = 3 a + c, the selection, p (through
+ * the same device function as the Welford, covariance and projection sweeps
+ * when d_xform and d_refinfo are both given, the raw floats when both are
+ * NULL) and d_i(f) = f64(p_i) - d_mean[i].
+ *   d_y[i * ldy + c] = (accumulate ? d_y[i * ldy + c] : 0)
+ *                      + sum_f d_i(f) d_p[f * ldp + c],  i < 3 n_sel, c < n_cols
+ *       (d_p f64 [n_frames][ldp >= n_cols], row f = frame f of the batch; d_y
+ *       f64 [3 n_sel][ldy >= n_cols]; 1 <= n_cols <= 48; columns >= n_cols of
+ *       either are neither read nor written).  accumulate = 1 is how a
+ *       streamed trajectory adds its batches, in batch order.  n_frames = 0
+ *       is RMSF_OK and leaves d_y as it is.
+ * Work is cut into (16 atoms = 48 coordinates, frame range) workgroups.  With
+ * more than one frame range (few atoms, many frames) the partials go to d_work
+ * (rmsf_pca_backproject_workspace_bytes() bytes, 0 when none is needed and
+ * d_work may be NULL) and are summed in frame-range order by a second launch,
+ * from d_y when accumulating and else from the first range's partial (so a
+ * sum of negative zeros keeps its sign, as the one-range path's store does):
+ * no floating-point atomics.  The plan is a function of (n_frames, n_sel,
+ * n_cols) alone: the same bits for the same inputs and batching.
+ * rmsf_pca_backproject_workspace_bytes is host-only arithmetic (no device).
+ * Bad arguments (a NULL pointer, n_cols < 1 or > 48, ldp or ldy < n_cols, one
+ * of d_xform and d_refinfo without the other, a workspace too small):
+ * RMSF_EINVAL, before any launch.                                           */
+size_t rmsf_pca_backproject_workspace_bytes(int64_t n_frames, int64_t n_sel,
+                                            int64_t n_cols);
+int rmsf_pca_backproject(const float *d_xyz, int64_t frame_stride,
+                         int64_t n_frames, int64_t n_sel, const int32_t *d_sel,
+                         const double *d_xform, const double *d_refinfo,
+                         const double *d_mean, const double *d_p, int64_t ldp,
+                         int64_t n_cols, double *d_y, int64_t ldy,
+                         int accumulate, void *d_work, size_t work_bytes,
+                         void *stream);
 
 /* ---- block products of a device-side eigen-solver (PCA(solver="device")) ---
  * The three products of a blocked subspace iteration with Rayleigh-Ritz on a

@@ -10,7 +10,9 @@ Public surface (mirrors the reference's names):
     (``RMSF(..., covariance=True)``), named as MDAnalysis.analysis.pca.PCA names them;
     ``PCA.transform`` projects a trajectory on them on the device, ``cosine_content``
     measures such a projection's convergence; ``PCA(solver="device")`` finds the first modes
-    on the device (``rmsf_amd.eigen.top_eigenpairs``) and raises ``PCAConvergenceError`` when it cannot
+    on the device (``rmsf_amd.eigen.top_eigenpairs``) and raises ``PCAConvergenceError`` when it cannot;
+    ``PCA(solver="matrix_free")`` finds them from the trajectory with no [3n, 3n] matrix at all;
+    ``rmsip`` / ``cumulative_overlap`` compare two sets of modes
   * ``DistanceMatrix`` / ``DiffusionMap`` -- the all-pairs RMSD matrix of the frames and
     its diffusion map, named as MDAnalysis.analysis.diffusionmap names them
 """
@@ -20,7 +22,7 @@ from .qcprot import CalcRMSDRotationalMatrix, get_rotation_matrix
 from .moments import second_order_moments
 from .rms import RMSF, Results
 from .eigen import PCAConvergenceError
-from .pca import PCA, cosine_content, pca_from_comoment
+from .pca import PCA, cosine_content, cumulative_overlap, pca_from_comoment, rmsip
 from .distances import DiffusionMap, DistanceMatrix
 
 __all__ = [
@@ -29,6 +31,8 @@ __all__ = [
     "PCA",
     "pca_from_comoment",
     "cosine_content",
+    "rmsip",
+    "cumulative_overlap",
     "PCAConvergenceError",
     "DistanceMatrix",
     "DiffusionMap",

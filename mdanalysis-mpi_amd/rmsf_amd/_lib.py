@@ -23,7 +23,7 @@ RMSF_MODE_SUM = 1
 RMSF_XFORM_DOUBLES = 16
 RMSF_MAX_SPLIT_FRAMES = 4096  # frames per accumulate split (Welford coefficient table)
 RMSF_REFINFO_DOUBLES = 2064  # 16-double record + reduction scratch
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 
 class RmsfError(RuntimeError):
@@ -104,6 +104,9 @@ SIGNATURES = {
     "rmsf_pca_project_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "rmsf_pca_project": (c_int, [P, c_int64, c_int64, c_int64, P, P, P, P, P, c_int64, c_int64, P, c_int64, P, c_size_t,
                                  P]),
+    "rmsf_pca_backproject_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "rmsf_pca_backproject": (c_int, [P, c_int64, c_int64, c_int64, P, P, P, P, P, c_int64, c_int64, P, c_int64, c_int,
+                                     P, c_size_t, P]),
     "rmsf_symm_block_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "rmsf_symm_block": (c_int, [P, c_int64, c_int64, P, c_int64, c_int64, P, c_int64, P, c_size_t, P]),
     "rmsf_block_gram_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),

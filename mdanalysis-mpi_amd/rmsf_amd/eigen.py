@@ -9,7 +9,10 @@ The matrix is touched through three block products only,
 
 so the same driver runs over ``DeviceOps`` (csrc/eigen_block.hip on the f64
 matrix cores, the matrix and every block in HBM) and over ``NumpyOps`` (the
-whole iteration, its stopping rule and its breakdown paths on the CPU).  The
+whole iteration, its stopping rule and its breakdown paths on the CPU).
+``TrajectoryOps`` overrides ``symm`` alone: M Q = D^T (D Q) / denom from the
+trajectory's frames (csrc/pca_project.hip and csrc/pca_backproject.hip), so no
+n x n matrix exists at all; ``FactorOps`` is its numpy twin.  The
 b x b steps -- ``numpy.linalg.eigh`` of a Gram matrix or of the projected
 matrix -- run on the host: a few stream synchronisations per iteration.
 
@@ -141,6 +144,161 @@ class DeviceOps:
         c = self.eng.empty(self.n, nc)
         self.eng.block_update(alpha, a, b, nb, self.put(t), self.n, nc, c)
         return c
+
+
+class FactorOps(NumpyOps):
+    """The numpy twin of ``TrajectoryOps``: the matrix D^T D / denom through
+    its factor ``d`` [F, n] alone, ``symm(q) = d.T @ (d @ q) / denom``.  The
+    n x n matrix is never formed."""
+
+    def __init__(self, d, denom: float):
+        d = np.asarray(d, dtype=np.float64)
+        if d.ndim != 2:
+            raise ValueError("d must be [n_frames, n]")
+        if not float(denom) > 0.0:
+            raise ValueError(f"denom must be positive, got {denom}")
+        self.d, self.denom, self.n = d, float(denom), d.shape[1]
+
+    def symm(self, q):
+        return self.d.T @ (self.d @ q) / self.denom
+
+
+_TRAJ_ONE_DEVICE = "the matrix-free product runs on one device per process: not "
+_TRAJ_PLANES = ('the matrix-free product reads (frame, atom, xyz) rows; HBM-resident coordinate planes are not '
+                'supported -- pass the trajectory with layout="fac"')
+
+
+class TrajectoryOps(DeviceOps):
+    """The covariance as an operator on the trajectory, with no [n, n] matrix
+    anywhere (n = 3 n_sel):
+
+        symm(Q) = D^T (D Q) / denom,   D[f, i] = x_i(f) - mean[i]
+
+    where x(f) is frame f's selected coordinates, superposed exactly as the
+    run's last sweep superposed them when ``aligned`` -- the rows
+    ``PCA.transform`` projects.  D Q is csrc/pca_project.hip, its adjoint
+    csrc/pca_backproject.hip, both on the f64 matrix cores, batch by batch in
+    the source's order; ``put``, ``get``, ``gram`` and ``update`` are
+    ``DeviceOps``' own and need only n.
+
+    ``source``, ``frames``: the frame source and ``FrameList`` of the run
+    (``RMSF._last_run``), with its ``masses``, device ``ref`` / ``refinfo``
+    and ``exact``.  ``mean``: f64 [n] (host or HBM), ``denom``: n_frames -
+    ddof.  ``batch_frames`` bounds a batch, and with it the scratch P_b
+    [batch, b]; default: every frame at once for a source that yields them so
+    -- 8 b F bytes, under the trajectory's own 12 n_sel F from 32 atoms on.
+
+    With ``aligned`` every frame's transform record is computed once, on the
+    first product, into an HBM [F, RMSF_XFORM_DOUBLES] tensor -- by
+    ``Superposer.run`` on the frame-parallel path, ``superpose_seq`` when the
+    run was exact, as ``PCA.transform`` computes them -- and later products
+    read the records: an iteration costs two reads of a batch, not four.
+
+    One device per process: HBM-resident ``layout="soa"`` planes and a
+    ``torch.distributed`` world of more than one rank are NotImplementedError
+    before any launch."""
+
+    def __init__(self, source, frames, mean, denom: float, *, masses=None, aligned: bool = False, exact: bool = False,
+                 ref=None, refinfo=None, batch_frames: int | None = None, engine=None, device=None):
+        import torch
+
+        from . import parallel
+        from .engine import Engine
+        from .sources import DeviceSource
+        if isinstance(source, (list, tuple)):
+            raise NotImplementedError(_TRAJ_ONE_DEVICE + "with gpus= or a list of shards")
+        if isinstance(source, DeviceSource) and source.layout == "soa":
+            raise NotImplementedError(_TRAJ_PLANES)
+        if parallel.world()[1] > 1:
+            raise NotImplementedError(_TRAJ_ONE_DEVICE + "under torch.distributed with more than one rank")
+        if not float(denom) > 0.0:
+            raise ValueError(f"denom must be positive, got {denom}")
+        if aligned and (ref is None or refinfo is None):
+            raise ValueError("an aligned product needs the run's device reference (ref, refinfo)")
+        self.eng = engine or Engine(device)
+        self.src, self.frames = source, frames
+        self.n_sel, self.n = int(source.n_sel), 3 * int(source.n_sel)
+        self.n_frames = len(frames)
+        self.denom = float(denom)
+        self.aligned, self.exact = bool(aligned), bool(exact)
+        self.ref, self.refinfo, self.masses = ref, refinfo, masses
+        self.max_batch = max(1, min(int(batch_frames or self.n_frames or 1), max(1, self.n_frames)))
+        if isinstance(mean, torch.Tensor):
+            mean = mean.detach().cpu().numpy()
+        m = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        if m.size != self.n:
+            raise ValueError(f"mean must have {self.n} entries, got {m.size}")
+        with torch.cuda.device(self.eng.device):
+            self.mean = torch.as_tensor(m).to(self.eng.device)
+        self._work = self._p = self._records = None
+
+    def _batches(self):
+        return self.src.batches(self.frames, 0, self.n_frames, self.max_batch, self.eng.stream)
+
+    def _superpose_all(self):
+        """Every frame's transform record, once: [F, RMSF_XFORM_DOUBLES]."""
+        import torch
+
+        from ._lib import RMSF_XFORM_DOUBLES
+        from .pipeline import Superposer
+        eng, n_sel = self.eng, self.n_sel
+        rec = eng.empty(max(1, self.n_frames), RMSF_XFORM_DOUBLES)
+        m_dev, mass_total, sup = None, float(n_sel), None
+        if self.masses is not None:
+            m_np = np.ascontiguousarray(self.masses, dtype=np.float64)
+            mass_total = float(m_np.sum())  # numpy's own sum, as the exact run's (pipeline._run_exact)
+            m_dev = torch.as_tensor(m_np).to(eng.device)
+        if not self.exact:
+            sup = Superposer(eng, n_sel, self.max_batch, m_dev)
+        done = 0
+        for b in self._batches():
+            if b.pstride:
+                raise NotImplementedError(_TRAJ_PLANES)
+            x = rec[done:done + b.n_frames]
+            if self.exact:
+                eng.superpose_seq(b.ptr, b.fstride, b.n_frames, n_sel, b.sel, m_dev, mass_total, self.ref,
+                                  self.refinfo, x)
+            else:
+                x.copy_(sup.run(b, self.ref, self.refinfo))
+            done += b.n_frames
+            b.done()
+        if done != self.n_frames:
+            raise RuntimeError(f"the source yielded {done} of {self.n_frames} frames")
+        return rec
+
+    def symm(self, q):
+        import torch
+
+        eng, n_sel = self.eng, self.n_sel
+        b_cols = int(q.shape[1])
+        with torch.cuda.device(eng.device):
+            if self.aligned and self._records is None:
+                self._records = self._superpose_all()
+            if self._p is None or self._p.shape[1] < b_cols:
+                self._p = eng.empty(self.max_batch, max(b_cols, MAX_BLOCK))
+            y = eng.empty(self.n, b_cols)
+            done = 0
+            for i, b in enumerate(self._batches()):
+                if b.pstride:
+                    raise NotImplementedError(_TRAJ_PLANES)
+                x = self._records[done:done + b.n_frames] if self.aligned else None
+                info = self.refinfo if self.aligned else None
+                need = max(eng.pca_project_workspace_bytes(b.n_frames, n_sel, b_cols),
+                           eng.pca_backproject_workspace_bytes(b.n_frames, n_sel, b_cols))
+                work = self._scratch(need)  # the two launches follow each other on one stream
+                eng.pca_project(b.ptr, b.fstride, b.n_frames, n_sel, b.sel, x, info, self.mean, q, b_cols, self._p,
+                                work)
+                eng.pca_backproject(b.ptr, b.fstride, b.n_frames, n_sel, b.sel, x, info, self.mean, self._p, b_cols,
+                                    y, i > 0, work)
+                done += b.n_frames
+                b.done()
+            if done != self.n_frames:
+                raise RuntimeError(f"the source yielded {done} of {self.n_frames} frames")
+            if done == 0:
+                y.zero_()
+            flat = y.view(-1)
+            eng.divide(flat, self.denom, flat)
+        return y
 
 
 def svqb_transform(g: np.ndarray):

@@ -436,6 +436,30 @@ class Engine:
              mean.data_ptr(), comp.data_ptr(), comp.stride(0), n_comp, out.data_ptr(), out.stride(0), _ptr(work),
              0 if work is None else work.numel() * work.element_size(), self.stream)
 
+    # -- PCA back-projection (csrc/pca_backproject.hip) --------------------------
+    def pca_backproject_workspace_bytes(self, n_frames: int, n_sel: int, n_cols: int) -> int:
+        return int(self.lib.rmsf_pca_backproject_workspace_bytes(n_frames, n_sel, n_cols))
+
+    def pca_backproject(self, xyz_ptr: int, fstride: int, n_frames: int, n_sel: int, sel, xform, refinfo,
+                        mean: torch.Tensor, p: torch.Tensor, n_cols: int, y: torch.Tensor, accumulate: bool = False,
+                        work: torch.Tensor | None = None) -> None:
+        """y[i, c] (+)= sum_f d_i(f) p[f, c] for c < ``n_cols`` <= 48 over the
+        batch, the adjoint of ``pca_project`` with the same d = f64(p) - mean
+        (rmsf_pca_backproject).  ``p``: f64 [>= n_frames, >= n_cols], ``y``:
+        f64 [>= 3 n_sel, >= n_cols], rows of either may be wider (their other
+        columns are not touched).  ``accumulate``: add to ``y`` (a later batch
+        of a streamed trajectory) instead of overwriting it.  ``work``: f64
+        scratch of at least pca_backproject_workspace_bytes(n_frames, n_sel,
+        n_cols) bytes (None when 0)."""
+        n = 3 * n_sel
+        if (mean.dtype != F64 or p.dtype != F64 or y.dtype != F64 or p.dim() != 2 or y.dim() != 2
+                or p.stride(1) != 1 or y.stride(1) != 1 or mean.numel() < n or not mean.is_contiguous()
+                or p.shape[0] < n_frames or p.shape[1] < n_cols or y.shape[0] < n or y.shape[1] < n_cols):
+            raise ValueError("pca_backproject: buffer sizes")
+        call("rmsf_pca_backproject", xyz_ptr, fstride, n_frames, n_sel, _ptr(sel), _ptr(xform), _ptr(refinfo),
+             mean.data_ptr(), p.data_ptr(), p.stride(0), n_cols, y.data_ptr(), y.stride(0), int(bool(accumulate)),
+             _ptr(work), 0 if work is None else work.numel() * work.element_size(), self.stream)
+
     # -- block products of the device eigen-solver (csrc/eigen_block.hip) -------
     @staticmethod
     def _is_block(t: torch.Tensor, rows: int, cols: int) -> bool:

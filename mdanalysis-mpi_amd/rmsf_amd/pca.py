@@ -8,7 +8,10 @@ matrix on the device (csrc/covariance.hip, the f64 matrix cores) from the
 very coordinates the Welford sweep reads; the eigen-decomposition of the
 [3n, 3n] f64 matrix is ``numpy.linalg.eigh`` on the host, or, with
 ``solver="device"``, the first modes by subspace iteration on the matrix where
-it lies (rmsf_amd/eigen.py over csrc/eigen_block.hip).
+it lies (rmsf_amd/eigen.py over csrc/eigen_block.hip), or, with
+``solver="matrix_free"``, the same iteration over the trajectory itself with
+no matrix formed at all (csrc/pca_project.hip and csrc/pca_backproject.hip).
+``rmsip`` and ``cumulative_overlap`` compare two sets of modes.
 
 ``PCA.transform()`` projects a trajectory on the components, on the device
 (csrc/pca_project.hip, the f64 matrix cores again): every frame is superposed
@@ -98,6 +101,65 @@ def cosine_content(pca_space, i: int) -> float:
     return float(2.0 / big_t * _simpson(cos * col) ** 2 / _simpson(col * col))
 
 
+def _mode_sets(a, b, n_components):
+    """The first columns of two sets of modes [n, ka], [n, kb] over the same
+    coordinates, as f64."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if a.ndim != 2 or b.ndim != 2:
+        raise ValueError("modes must be [n_coordinates, n_components] (columns, as results.p_components)")
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"the two sets of modes span {a.shape[0]} and {b.shape[0]} coordinates")
+    if n_components is None:
+        ka, kb = a.shape[1], b.shape[1]
+    elif isinstance(n_components, (tuple, list)):
+        ka, kb = (int(n) for n in n_components)
+    else:
+        ka = kb = int(n_components)
+    if not (1 <= ka <= a.shape[1] and 1 <= kb <= b.shape[1]):
+        raise ValueError(f"n_components must be in 1..{a.shape[1]} and 1..{b.shape[1]}, got {n_components}")
+    return a[:, :ka], b[:, :kb]
+
+
+def rmsip(a, b, n_components=None) -> float:
+    """The root mean square inner product of two sets of modes, columns of
+    ``a`` [n, ka] and ``b`` [n, kb] (``results.p_components`` of two runs):
+
+        sqrt(sum_ij (a_i . b_j)^2 / ka)
+
+    over the first ``n_components`` columns of each (an int, a pair, default
+    all).  1 when orthonormal sets span the same subspace, 0 when the two are
+    orthogonal (Amadei et al., Proteins 36:419, 1999).  Host numpy.  Restated
+    from MDAnalysis' documentation of ``MDAnalysis.analysis.pca.rmsip``, not
+    verified against it."""
+    a, b = _mode_sets(a, b, n_components)
+    dot = a.T @ b
+    return float(np.sqrt((dot * dot).sum() / a.shape[1]))
+
+
+def cumulative_overlap(a, b, i: int = 0, n_components=None) -> float:
+    """How well the modes ``b`` [n, kb] (columns; the first ``n_components``,
+    default all) span column ``i`` of ``a`` [n, ka]:
+
+        sqrt(sum_j (a_i . b_j)^2 / (|a_i|^2 |b_j|^2))
+
+    1 for a vector inside the span of orthogonal modes, 0 for one orthogonal
+    to all of them.  Host numpy.  Restated from MDAnalysis' documentation of
+    ``MDAnalysis.analysis.pca.cumulative_overlap``, not verified against it."""
+    a, b = _mode_sets(a, b, None)
+    if n_components is not None:
+        if not 1 <= int(n_components) <= b.shape[1]:
+            raise ValueError(f"n_components must be in 1..{b.shape[1]}, got {n_components}")
+        b = b[:, :int(n_components)]
+    if not 0 <= int(i) < a.shape[1]:
+        raise ValueError(f"i must be in 0..{a.shape[1] - 1}, got {i}")
+    vec = a[:, int(i)]
+    norms = np.sqrt((vec * vec).sum()) * np.sqrt((b * b).sum(axis=0))
+    if not np.all(norms > 0.0):
+        raise ValueError("cumulative_overlap of a zero vector")
+    o = np.abs(vec @ b) / norms
+    return float(np.sqrt((o * o).sum()))
+
+
 _ONE_DEVICE = "PCA.transform runs on one device per process: not "
 _PLANES = ('PCA.transform reads (frame, atom, xyz) rows; HBM-resident coordinate planes are not supported -- pass '
            'the trajectory with layout="fac"')
@@ -148,25 +210,43 @@ class PCA:
     than ``n_components`` significant directions (a one-frame run) or an
     iteration that does not converge raises ``PCAConvergenceError``.  Every
     rank that holds the matrix runs the same deterministic solve.
+
+    ``solver="matrix_free"`` runs the same iteration with no [3n, 3n] matrix
+    anywhere: ``RMSF`` without the covariance gives the mean, and the product
+    M Q = D^T (D Q) / (n_frames - ddof) is taken from the trajectory itself
+    (``rmsf_amd.eigen.TrajectoryOps``: csrc/pca_project.hip and its adjoint
+    csrc/pca_backproject.hip, two reads of the frames per iteration, O(3n b)
+    memory), so the selection may be as large as the trajectory that fits --
+    the covariance's memory check is never asked.  ``n_components`` (1..40),
+    ``tol``, ``max_iter``, ``seed``, ``results.p_components``, ``variance`` and
+    ``solver_info`` are as with ``"device"``; ``results.covariance`` is None,
+    and ``cumulated_variance`` divides by the trace taken from the Welford
+    sums, ``results.sumsquares.sum() / (n_frames - ddof)``.  Fewer than
+    ``n_components`` directions (n_frames - ddof < n_components) raise
+    ``PCAConvergenceError``.  One device per process, as ``transform()``:
+    ``gpus=``, lists of shards, HBM-resident ``layout="soa"`` planes and more
+    than one ``torch.distributed`` rank are NotImplementedError before any
+    launch.  ``transform()`` works after it as after the other solvers.
     """
 
     def __init__(self, atomgroup, select=None, align="average", n_components: int | None = None, ddof: int = 1,
                  solver: str = "host", tol: float = 1e-10, max_iter: int = 300, seed: int = 0, **rmsf_kwargs):
-        if solver not in ("host", "device"):
-            raise ValueError(f'solver must be "host" or "device", got {solver!r}')
-        if solver == "device":
+        if solver not in ("host", "device", "matrix_free"):
+            raise ValueError(f'solver must be "host", "device" or "matrix_free", got {solver!r}')
+        if solver != "host":
             if n_components is None:
-                raise ValueError('solver="device" computes the first n_components modes: give n_components (a full '
-                                 'decomposition is solver="host"\'s job)')
+                raise ValueError(f'solver="{solver}" computes the first n_components modes: give n_components (a '
+                                 'full decomposition is solver="host"\'s job)')
             if not 1 <= int(n_components) <= MAX_COMPONENTS:
-                raise ValueError(f'solver="device" computes 1..{MAX_COMPONENTS} components, got {n_components}; use '
-                                 'solver="host" for more')
+                raise ValueError(f'solver="{solver}" computes 1..{MAX_COMPONENTS} components, got {n_components}; '
+                                 'use solver="host" for more')
         rmsf_kwargs.pop("covariance", None)
         self.n_components = n_components
         self.ddof = int(ddof)
         self.solver, self.tol, self.max_iter, self.seed = solver, float(tol), int(max_iter), int(seed)
-        self._rmsf = RMSF(atomgroup, select=select, align=align, covariance=True, **rmsf_kwargs)
+        self._rmsf = RMSF(atomgroup, select=select, align=align, covariance=solver != "matrix_free", **rmsf_kwargs)
         self._rmsf._comoment_stays_in_hbm = solver == "device"
+        self._rmsf._keep_last_run = solver == "matrix_free"
         self.results = Results()
 
     def _run_device(self, start, stop, step, frames, **kwargs):
@@ -205,9 +285,48 @@ class PCA:
         self.n_frames = r.n_frames
         return self
 
+    def _run_matrix_free(self, start, stop, step, frames, **kwargs):
+        """``run()`` with ``solver="matrix_free"``: ``RMSF`` without the
+        covariance for the mean, the RMSF and the last sweep's reference, then
+        ``top_eigenpairs`` over ``TrajectoryOps``.  No [3n, 3n] matrix is
+        formed and ``check_covariance_memory`` is never asked."""
+        from .eigen import TrajectoryOps, block_width, top_eigenpairs
+
+        self._refuse_transform(None, 'PCA(solver="matrix_free")')  # before any launch
+        rm = self._rmsf
+        r = rm.run(start, stop, step, frames=frames, **kwargs).results
+        out = self.results
+        out.n_frames = r.n_frames
+        out.mean, out.rmsf = r.mean, r.rmsf
+        out.covariance = None
+        k = int(self.n_components)
+        denom = r.n_frames - self.ddof
+        if denom <= 0:  # one frame: every deviation is zero and there is nothing to divide by
+            info = {"n_iter": 0, "residuals": np.full(k, np.inf), "rank": 0, "block": 0, "converged": False}
+            out.solver_info = info
+            raise PCAConvergenceError(f"asked for {k} components, the matrix has rank 0: {r.n_frames} frame(s) with "
+                                      f"ddof = {self.ddof} leave no covariance", info)
+        block_width(r.mean.size, k)  # ValueError for k > 3n, before any launch
+        last = rm._last_run
+        import torch
+
+        with torch.cuda.device(last["device"]):
+            ops = TrajectoryOps(last["source"], last["frames"], r.mean, float(denom), masses=last["masses"],
+                                aligned=rm.align is not None, exact=last["exact"], ref=last["ref"],
+                                refinfo=last["refinfo"], batch_frames=rm.batch_frames, device=last["device"])
+            out.variance, out.p_components, out.solver_info = top_eigenpairs(
+                None, k, tol=self.tol, max_iter=self.max_iter, seed=self.seed, ops=ops)
+        # the matrix's trace from the Welford sums: sum_i sum_f d_i(f)^2 / (F - ddof)
+        trace = float(np.asarray(r.sumsquares, dtype=np.float64).sum()) / float(denom)
+        out.cumulated_variance = np.cumsum(out.variance) / trace
+        self.n_frames = r.n_frames
+        return self
+
     def run(self, start=None, stop=None, step=None, frames=None, **kwargs):
         if self.solver == "device":
             return self._run_device(start, stop, step, frames, **kwargs)
+        if self.solver == "matrix_free":
+            return self._run_matrix_free(start, stop, step, frames, **kwargs)
         r = self._rmsf.run(start, stop, step, frames=frames, **kwargs).results
         out = self.results
         out.n_frames = r.n_frames
@@ -221,24 +340,27 @@ class PCA:
         self.n_frames = r.n_frames
         return self
 
-    def _refuse_transform(self, atomgroup) -> None:
+    def _refuse_transform(self, atomgroup, what: str = "PCA.transform") -> None:
+        """What ``transform`` -- and ``solver="matrix_free"``, which reads the
+        trajectory the same way (``what``) -- refuses, before any launch."""
         import torch
 
         from . import parallel
         from .sources import DeviceSource
 
+        one_device = _ONE_DEVICE.replace("PCA.transform", what)
         r = self._rmsf
         for x in (r._input, atomgroup):
             if isinstance(x, (list, tuple)):
-                raise NotImplementedError(_ONE_DEVICE + "with gpus= or a list of shards")
+                raise NotImplementedError(one_device + "with gpus= or a list of shards")
         if r.gpus is not None:
-            raise NotImplementedError(_ONE_DEVICE + "with gpus= or a list of shards")
+            raise NotImplementedError(one_device + "with gpus= or a list of shards")
         x = r._input if atomgroup is None else atomgroup
         if (isinstance(x, DeviceSource) and x.layout == "soa") or (
                 isinstance(x, torch.Tensor) and x.device.type == "cuda" and r.layout == "soa"):
-            raise NotImplementedError(_PLANES)
+            raise NotImplementedError(_PLANES.replace("PCA.transform", what))
         if parallel.world()[1] > 1:
-            raise NotImplementedError(_ONE_DEVICE + "under torch.distributed with more than one rank")
+            raise NotImplementedError(one_device + "under torch.distributed with more than one rank")
 
     def transform(self, atomgroup=None, n_components: int | None = None, start=None, stop=None, step=None,
                   frames=None, as_tensor: bool = False):

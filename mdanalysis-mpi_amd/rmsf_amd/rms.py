@@ -190,6 +190,7 @@ class RMSF:
         self._last_run = None
         self._comoment_stays_in_hbm = False  # private: set by PCA(solver="device")
         self._comoment_hbm = None
+        self._keep_last_run = False  # private: set by PCA(solver="matrix_free"), which forms no matrix
 
     # MDAnalysis AnalysisBase compatible signature
     def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
@@ -221,7 +222,7 @@ class RMSF:
                                collect_transforms=self.collect_transforms, merge_root=self.merge_root,
                                merge_scatter=self.merge_scatter, exact=self.exact, merge_order=self.merge_order,
                                **({"covariance": True} if self.covariance else {}))
-            if self.covariance:
+            if self.covariance or self._keep_last_run:
                 # what PCA.transform superposes with, exactly as the last sweep did: its source and frame
                 # list, the masses, the device reference and whether the sequential kernels ran
                 self._last_run = {"source": src, "frames": fl, "masses": masses, "device": eng.device,

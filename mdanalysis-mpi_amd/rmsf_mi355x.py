@@ -62,18 +62,19 @@ def main(argv=None) -> int:
                          "frames on its components, f64 [F, K] (PCA.transform; one process only)")
     ap.add_argument("--n-components", type=int, default=None, metavar="K",
                     help="--pca-transform: the number of components (default: all 3n)")
-    ap.add_argument("--pca-solver", choices=["host", "device"], default="host",
+    ap.add_argument("--pca-solver", choices=["host", "device", "matrix_free"], default="host",
                     help="--pca-transform: numpy.linalg.eigh on the host, or the first --n-components (<= 40) modes "
-                         "by subspace iteration on the device, the matrix staying in HBM")
+                         "by subspace iteration on the device: 'device' with the matrix staying in HBM, "
+                         "'matrix_free' from the trajectory alone, with no 3n x 3n matrix (any number of atoms)")
     a = ap.parse_args(argv)
     if a.pca_transform and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--pca-transform runs in one process (no torch.distributed launch)")
     if a.pca_transform and a.merge == "scatter":
         ap.error("--pca-transform needs --merge root or all")
-    if a.pca_solver == "device" and not a.pca_transform:
-        ap.error("--pca-solver device needs --pca-transform")
-    if a.pca_solver == "device" and a.n_components is None:
-        ap.error("--pca-solver device needs --n-components")
+    if a.pca_solver != "host" and not a.pca_transform:
+        ap.error(f"--pca-solver {a.pca_solver} needs --pca-transform")
+    if a.pca_solver != "host" and a.n_components is None:
+        ap.error(f"--pca-solver {a.pca_solver} needs --n-components")
     if a.dist_matrix and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--dist-matrix runs in one process (no torch.distributed launch)")
     if a.covariance and a.merge == "scatter":
