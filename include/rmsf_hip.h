@@ -696,6 +696,49 @@ int rmsf_pairwise_rmsd(const float *d_xyz, int64_t frame_stride,
                        double cutoff, double *d_out, int64_t ld, void *d_work,
                        size_t work_bytes, void *stream);
 
+/* ---- cross RMSD matrix: every frame of A against every frame of B ----------
+ * d_out[i * ld + j] = the RMSD of frame i of A (n_a frames at d_a + i *
+ * stride_a) and frame j of B (n_b frames at d_b + j * stride_b), ld >= n_b:
+ * the contraction, the epilogue and the cutoff of rmsf_pairwise_rmsd over the
+ * whole n_a x n_b rectangle, each pair once, one store a pair, nothing
+ * mirrored and no diagonal.  Each side has its own selection of n_sel atoms
+ * (d_sel_a, d_sel_b; NULL: atoms 0..n_sel-1), stride, centres and G; atom k of
+ * one selection is paired with atom k of the other and weighs d_weights[k]
+ * (NULL: 1), w_total = their sum.
+ * Centres and G of a side: rmsf_pairwise_centres(per_frame = 1) for
+ * superpose = 1.  superpose = 0 needs one common shift for both sides (tr A_ij
+ * and the G are taken about it): rmsf_pairwise_centres(per_frame = 0) for A,
+ * then rmsf_pairwise_centres_about for B with d_about = A's first centre
+ * (three doubles in device memory), which gives every frame that centre and G
+ * about it.
+ * Work is cut into (tile I of A, tile J of B, atom range) workgroups of 16 x
+ * 16 frames; with more than one atom range the partials go to d_work
+ * (rmsf_cross_workspace_bytes() bytes, 0 when none is needed) and are summed
+ * in atom order by a second launch.  The plan is a function of (n_a, n_b,
+ * n_sel) alone, there are no floating-point atomics: the same bits for the
+ * same inputs.  More than INT32_MAX tile pairs are refused.
+ * rmsf_row_argmin: of every row of d_m[n_rows][ld] (n_cols >= 1 entries), the
+ * least entry (d_val[n_rows], may be NULL) and the lowest column holding it
+ * (d_idx[n_rows], may be NULL) -- strict comparisons in a fixed order, so
+ * equal minima (exact zeros below the cutoff, duplicated references) resolve
+ * to the first; NaN entries are not ordered.                                */
+int rmsf_pairwise_centres_about(const float *d_xyz, int64_t frame_stride,
+                                int64_t n_frames, int64_t n_sel,
+                                const int32_t *d_sel, const double *d_weights,
+                                const double *d_about, double *d_centre,
+                                double *d_g, void *stream);
+size_t rmsf_cross_workspace_bytes(int64_t n_a, int64_t n_b, int64_t n_sel);
+int rmsf_cross_rmsd(const float *d_a, int64_t stride_a, int64_t n_a,
+                    const int32_t *d_sel_a, const double *d_centre_a,
+                    const double *d_g_a, const float *d_b, int64_t stride_b,
+                    int64_t n_b, const int32_t *d_sel_b,
+                    const double *d_centre_b, const double *d_g_b,
+                    int64_t n_sel, const double *d_weights, double w_total,
+                    int superpose, double cutoff, double *d_out, int64_t ld,
+                    void *d_work, size_t work_bytes, void *stream);
+int rmsf_row_argmin(const double *d_m, int64_t n_rows, int64_t n_cols,
+                    int64_t ld, int64_t *d_idx, double *d_val, void *stream);
+
 /* ---- qcprot.CalcRMSDRotationalMatrix (RMSF.py:48) --------------------------
  * Batched QCP on device: A[n][9], E0[n], atom counts N[n] -> rot[n][9],
  * rmsd[n].  Exposed for the upstream known-answer test.                      */

@@ -26,6 +26,17 @@
 //   * k_pw_fold     the split-K partials, summed in atom-range order.
 //   * pair_epilogue lambda by Newton's iteration (or the trace, without
 //                   superposition), the cutoff, the store and its mirror.
+//
+// The rectangle d[i, j] = RMSD(A_i, B_j) of two trajectories is the same
+// contraction with a second operand of its own (base, stride, selection,
+// centres, G):
+//
+//   * k_pw_cross_tiles  one workgroup per (tile I of A, tile J of B, atom
+//                       range), the whole tile rectangle; operand 0 is the A
+//                       tile and carries the weight.
+//   * k_pw_cross_fold   its split-K partials, summed in atom-range order.
+//   * cross_epilogue    pair_epilogue without the mirror: one store a pair.
+//   * k_row_argmin      one workgroup per row: the first least entry.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -91,25 +102,32 @@ __device__ __forceinline__ double block_sum(double v, double *__restrict__ sh) {
 }
 
 // One workgroup per frame f: c = sum_a w_a x_a / sum_a w_a over the frame
-// (over frame 0 when !per_frame: a common shift), then G = sum_a w_a |x_f,a - c|^2.
+// (over frame 0 when !per_frame: a common shift; `about`, three doubles, when
+// given: a shift found elsewhere), then G = sum_a w_a |x_f,a - c|^2.
 // Each thread adds its atoms in order, the threads are added by block_sum.
 template <bool GATHER>
 __global__ __launch_bounds__(kBlock) void k_pw_centres(const float *__restrict__ xyz, int64_t fstride, int64_t n_sel,
                                                        const int32_t *__restrict__ sel,
                                                        const double *__restrict__ weights, int per_frame,
+                                                       const double *__restrict__ about,
                                                        double *__restrict__ centre, double *__restrict__ g) {
   __shared__ double sh[kBlock];
   const int tid = threadIdx.x;
   const int64_t f = blockIdx.x;
-  const float *__restrict__ src = xyz + (per_frame ? f : 0) * fstride;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, sw = 0.0;
-  for (int64_t a = tid; a < n_sel; a += kBlock) {
-    const float *__restrict__ q = src + 3 * (GATHER ? (int64_t)sel[a] : a);
-    const double w = weights ? weights[a] : 1.0;
-    s0 += w * (double)q[0], s1 += w * (double)q[1], s2 += w * (double)q[2], sw += w;
+  double c0, c1, c2;
+  if (about) {  // (the same for every thread of the grid)
+    c0 = about[0], c1 = about[1], c2 = about[2];
+  } else {
+    const float *__restrict__ src = xyz + (per_frame ? f : 0) * fstride;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, sw = 0.0;
+    for (int64_t a = tid; a < n_sel; a += kBlock) {
+      const float *__restrict__ q = src + 3 * (GATHER ? (int64_t)sel[a] : a);
+      const double w = weights ? weights[a] : 1.0;
+      s0 += w * (double)q[0], s1 += w * (double)q[1], s2 += w * (double)q[2], sw += w;
+    }
+    s0 = block_sum(s0, sh), s1 = block_sum(s1, sh), s2 = block_sum(s2, sh), sw = block_sum(sw, sh);
+    c0 = s0 / sw, c1 = s1 / sw, c2 = s2 / sw;
   }
-  s0 = block_sum(s0, sh), s1 = block_sum(s1, sh), s2 = block_sum(s2, sh), sw = block_sum(sw, sh);
-  const double c0 = s0 / sw, c1 = s1 / sw, c2 = s2 / sw;
   const float *__restrict__ own = xyz + f * fstride;
   double gs = 0.0;
   for (int64_t a = tid; a < n_sel; a += kBlock) {
@@ -313,6 +331,258 @@ __global__ __launch_bounds__(kBlock) void k_pw_fold(const double *__restrict__ w
   pair_epilogue(A, I, J, n_frames, g, superpose, w_total, cutoff, out, ld, sd);
 }
 
+// ---- the rectangle: every frame of A against every frame of B ---------------
+
+static_assert(sizeof(double) * 2 * kKA * kPitch <= kLdsLimit, "the rectangle's sm fits");
+
+// One side of the rectangle: n frames at base + f fstride, their selection
+// (NULL: atoms 0..n_sel-1), centres and G.
+struct CrossSide {
+  const float *xyz;
+  int64_t fstride;
+  int64_t n;
+  const int32_t *sel;
+  const double *centre;
+  const double *g;
+};
+
+// A function of (n_a, n_b, n_sel) alone, as PwPlan is of (n_frames, n_sel).
+struct CrossPlan {
+  int64_t tiles_a, tiles_b;
+  int64_t n_pairs;   // tile pairs (I of A, J of B): pair = I tiles_b + J; 0 = more than a launch takes
+  int64_t n_ks;      // atom ranges; 1 = the epilogue runs in k_pw_cross_tiles
+  int64_t ks_atoms;  // atoms per range, a multiple of kKA
+};
+
+CrossPlan cross_plan(int64_t n_a, int64_t n_b, int64_t n_sel) {
+  CrossPlan p;
+  p.tiles_a = (n_a + kTF - 1) / kTF;
+  p.tiles_b = (n_b + kTF - 1) / kTF;
+  p.n_pairs = p.n_ks = p.ks_atoms = 0;
+  // (each factor first: the product of two int64 tile counts may not fit)
+  if (p.tiles_a > INT32_MAX || p.tiles_b > INT32_MAX || p.tiles_a * p.tiles_b > INT32_MAX) return p;
+  p.n_pairs = p.tiles_a * p.tiles_b;
+  const SplitK k = split_k(std::max<int64_t>(1, (n_sel + kKA - 1) / kKA), p.n_pairs, kTargetGroups, 1);
+  p.n_ks = k.n_ks;
+  p.ks_atoms = k.per * kKA;
+  return p;
+}
+
+size_t cross_work_doubles(const CrossPlan &p) {
+  if (p.n_ks <= 1) return 0;
+  return (size_t)p.n_ks * (size_t)p.n_pairs * kTile;
+}
+
+// Thread tid owns the pair (fi = tid >> 4 of A's tile I, fj = tid & 15 of B's
+// tile J) and its A_ij: pair_epilogue's arithmetic, one store, no mirror (fj
+// is the fastest index: the stores of 16 lanes run along a row).
+__device__ __forceinline__ void cross_epilogue(const double *A, int64_t I, int64_t J, int64_t n_a, int64_t n_b,
+                                               const double *__restrict__ g_a, const double *__restrict__ g_b,
+                                               int superpose, double w_total, double cutoff,
+                                               double *__restrict__ out, int64_t ld) {
+  const int tid = threadIdx.x;
+  const int64_t i = kTF * I + (tid >> 4), j = kTF * J + (tid & 15);
+  if (i >= n_a || j >= n_b) return;
+  const double gi = g_a[i], gj = g_b[j];
+  const double E0 = (gi + gj) * 0.5;
+  double d;
+  if (superpose) {
+    // (two all-zero frames: the quartic is 0 / 0; their distance is 0)
+    const double l = E0 > 0.0 || E0 != E0 ? qcp_lambda(A, E0) : E0;
+    d = sqrt(fabs(2.0 * (E0 - l)) / w_total);
+  } else {
+    d = sqrt(fabs(gi + gj - 2.0 * (A[0] + A[4] + A[8])) / w_total);
+  }
+  if (d <= cutoff) d = 0.0;
+  out[i * ld + j] = d;
+}
+
+// k_pw_tiles over the tile rectangle, each operand with a side of its own:
+// tile pair blockIdx.x = I tiles_b + J, atoms [blockIdx.y ks_atoms, ...).
+// Staging, the MFMA operands and the accumulators' meaning are k_pw_tiles';
+// operand 0 is A's tile I (times the weight), operand 1 B's tile J, both
+// always staged -- a tile of A and a tile of B are different data.  GATHER:
+// either side may have a selection (which, is the same for the whole grid).
+template <bool GATHER, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock, 2) void k_pw_cross_tiles(CrossSide sa, CrossSide sb, int64_t n_sel,
+                                                           const double *__restrict__ weights, int superpose,
+                                                           double w_total, double cutoff,
+                                                           double *__restrict__ out, int64_t ld,
+                                                           double *__restrict__ work, int64_t tiles_b,
+                                                           int64_t n_pairs, int64_t ks_atoms, int direct) {
+  __shared__ double sm[2 * kKA * kPitch];  // A then B deviations; reused for the waves' sum
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int ta = tid & (kAtomLanes - 1), tf = tid >> 4;
+  const int64_t pair = blockIdx.x, ks = blockIdx.y;
+  const int64_t I = pair / tiles_b, J = pair - I * tiles_b;
+
+  const int64_t a0 = ks * ks_atoms;
+  const int64_t a1 = a0 + ks_atoms < n_sel ? a0 + ks_atoms : n_sel;
+
+  // As in k_pw_tiles: a lane past a side's last frame reads that side's last
+  // frame, an atom past the range's end the range's last atom; every load is
+  // unconditional and in bounds, and its deviation is zeroed after.
+  const float *p_op[2];
+  const int32_t *sel_op[2];
+  double cen[2][3];
+  bool live[2];
+#pragma unroll
+  for (int op = 0; op < 2; ++op) {
+    const CrossSide &sd = op ? sb : sa;
+    const int64_t f = kTF * (op ? J : I) + tf;
+    live[op] = f < sd.n;
+    const int64_t fc = live[op] ? f : sd.n - 1;
+    p_op[op] = sd.xyz + fc * sd.fstride;
+    sel_op[op] = sd.sel;
+    cen[op][0] = sd.centre[3 * fc], cen[op][1] = sd.centre[3 * fc + 1], cen[op][2] = sd.centre[3 * fc + 2];
+  }
+
+  f64x4 acc[3][3];
+  zero_3x3(acc);
+
+  const double *sA = sm;
+  const double *sB = sm + kKA * kPitch;
+
+  float raw[2][kPasses][3];
+  double wv[kPasses];
+  auto prefetch = [&](int64_t ab) {
+#pragma unroll
+    for (int pass = 0; pass < kPasses; ++pass) {
+      const int64_t a = ab + pass * kAtomLanes + ta;
+      const int64_t ac = a < a1 ? a : a1 - 1;
+      if (WEIGHTED) wv[pass] = weights[ac];
+#pragma unroll
+      for (int op = 0; op < 2; ++op) {
+        const int64_t row = 3 * (GATHER && sel_op[op] ? (int64_t)sel_op[op][ac] : ac);
+        const float *__restrict__ q = p_op[op] + row;
+        raw[op][pass][0] = q[0], raw[op][pass][1] = q[1], raw[op][pass][2] = q[2];
+      }
+    }
+  };
+  prefetch(a0);
+
+  for (int64_t ab = a0; ab < a1; ab += kKA) {
+    // ---- stage kKA atoms of both operand tiles (zeros past either edge)
+#pragma unroll
+    for (int op = 0; op < 2; ++op) {
+#pragma unroll
+      for (int pass = 0; pass < kPasses; ++pass) {
+        const int k = pass * kAtomLanes + ta;
+        const bool on = live[op] && ab + k < a1;
+        double d0 = on ? (double)raw[op][pass][0] - cen[op][0] : 0.0;
+        double d1 = on ? (double)raw[op][pass][1] - cen[op][1] : 0.0;
+        double d2 = on ? (double)raw[op][pass][2] - cen[op][2] : 0.0;
+        if (WEIGHTED && op == 0) d0 *= wv[pass], d1 *= wv[pass], d2 *= wv[pass];
+        double *__restrict__ o = sm + (op * kKA + k) * kPitch + tf;
+        o[0] = d0, o[kTF] = d1, o[2 * kTF] = d2;
+      }
+    }
+    __syncthreads();
+    // (after the barrier: its fence waits for every load in flight)
+    if (ab + kKA < a1) prefetch(ab + kKA);
+    // ---- contract: wave w takes atoms [8 w, 8 w + 8) of the staged tile
+#pragma unroll
+    for (int s = 0; s < kKA / (4 * kWaves); ++s) {
+      const int k = (kKA / kWaves) * wave + 4 * s + (lane >> 4);
+      const double *__restrict__ ra = sA + k * kPitch + (lane & 15);
+      const double *__restrict__ rb = sB + k * kPitch + (lane & 15);
+      const double x0 = ra[0], x1 = ra[kTF], x2 = ra[2 * kTF];
+      const double y0 = rb[0], y1 = rb[kTF], y2 = rb[2 * kTF];
+      mfma_3x3(acc, x0, x1, x2, y0, y1, y2);
+    }
+    __syncthreads();
+  }
+
+  wave_sum_3x3(acc, sm, lane, wave,
+               [](int i, int j, int row, int col) { return kPairs * (3 * i + j) + kTF * row + col; });
+
+  if (direct) {
+    double A[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) A[q] = sm[kPairs * q + tid];
+    cross_epilogue(A, I, J, sa.n, sb.n, sa.g, sb.g, superpose, w_total, cutoff, out, ld);
+  } else {
+    double *__restrict__ w = work + ((int64_t)ks * n_pairs + pair) * kTile;
+    for (int e = tid; e < kTile; e += kBlock) w[e] = sm[e];
+  }
+}
+
+// The n_ks partials of every A_ij entry, summed in atom-range order, then
+// the epilogue.  One workgroup per tile pair.
+__global__ __launch_bounds__(kBlock) void k_pw_cross_fold(const double *__restrict__ work, int64_t n_a, int64_t n_b,
+                                                          int64_t tiles_b, int64_t n_pairs, int64_t n_ks,
+                                                          const double *__restrict__ g_a,
+                                                          const double *__restrict__ g_b, int superpose,
+                                                          double w_total, double cutoff, double *__restrict__ out,
+                                                          int64_t ld) {
+  const int tid = threadIdx.x;
+  const int64_t pair = blockIdx.x;
+  const int64_t I = pair / tiles_b, J = pair - I * tiles_b;
+  double A[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    const double *__restrict__ w = work + pair * kTile + kPairs * q + tid;
+    double s = 0.0;
+    for (int64_t k = 0; k < n_ks; ++k) s += w[k * n_pairs * kTile];
+    A[q] = s;
+  }
+  cross_epilogue(A, I, J, n_a, n_b, g_a, g_b, superpose, w_total, cutoff, out, ld);
+}
+
+// One workgroup per row of m[n_rows][ld]: its least entry and that entry's
+// lowest column.  Thread t scans columns t, t + 256, ... in order with a
+// strict <, so it keeps the first of equal values; the threads are then
+// joined by a halving tree that prefers the lower column among equal values --
+// the result is the same as one left-to-right scan.
+__global__ __launch_bounds__(kBlock) void k_row_argmin(const double *__restrict__ m, int64_t n_cols, int64_t ld,
+                                                       int64_t *__restrict__ idx, double *__restrict__ val) {
+  __shared__ double sv[kBlock];
+  __shared__ int64_t si[kBlock];
+  const int tid = threadIdx.x;
+  const double *__restrict__ row = m + (int64_t)blockIdx.x * ld;
+  double bv = INFINITY;
+  int64_t bi = INT64_MAX;  // a thread without a column never wins a tie
+  if (tid < n_cols) bv = row[tid], bi = tid;
+  for (int64_t c = (int64_t)tid + kBlock; c < n_cols; c += kBlock) {
+    const double v = row[c];
+    if (v < bv) bv = v, bi = c;
+  }
+  sv[tid] = bv, si[tid] = bi;
+  __syncthreads();
+  for (int s = kBlock / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      const double ov = sv[tid + s];
+      const int64_t oi = si[tid + s];
+      if (ov < sv[tid] || (ov == sv[tid] && oi < si[tid])) sv[tid] = ov, si[tid] = oi;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (idx) idx[blockIdx.x] = si[0];
+    if (val) val[blockIdx.x] = sv[0];
+  }
+}
+
+// k_pw_centres for n_frames frames, about each frame's own centre, frame 0's
+// (per_frame = 0) or d_about (when given).  The arguments are the caller's,
+// already checked; `who` names it in the message.
+int launch_centres(const char *who, const float *d_xyz, int64_t fstride, int64_t n_frames, int64_t n_sel,
+                   const int32_t *d_sel, const double *d_weights, int per_frame, const double *d_about,
+                   double *d_centre, double *d_g, void *stream) {
+  if (n_frames > INT32_MAX) return fail(RMSF_EINVAL, std::string(who) + ": too many frames for one launch");
+  if (n_frames == 0) return RMSF_OK;
+  const dim3 grid((unsigned)n_frames), block(kBlock);
+  if (d_sel)
+    hipLaunchKernelGGL(k_pw_centres<true>, grid, block, 0, S(stream), d_xyz, fstride, n_sel, d_sel, d_weights,
+                       per_frame, d_about, d_centre, d_g);
+  else
+    hipLaunchKernelGGL(k_pw_centres<false>, grid, block, 0, S(stream), d_xyz, fstride, n_sel, d_sel, d_weights,
+                       per_frame, d_about, d_centre, d_g);
+  return after_launch("k_pw_centres");
+}
+
 }  // namespace
 
 extern "C" {
@@ -322,16 +592,17 @@ RMSF_EXPORT int rmsf_pairwise_centres(const float *d_xyz, int64_t fstride, int64
                                       double *d_centre, double *d_g, void *stream) {
   if (!d_xyz || !d_centre || !d_g || n_sel < 1 || n_frames < 0 || fstride < 0)
     return fail(RMSF_EINVAL, "rmsf_pairwise_centres: bad arguments");
-  if (n_frames > INT32_MAX) return fail(RMSF_EINVAL, "rmsf_pairwise_centres: too many frames for one launch");
-  if (n_frames == 0) return RMSF_OK;
-  const dim3 grid((unsigned)n_frames), block(kBlock);
-  if (d_sel)
-    hipLaunchKernelGGL(k_pw_centres<true>, grid, block, 0, S(stream), d_xyz, fstride, n_sel, d_sel, d_weights,
-                       per_frame, d_centre, d_g);
-  else
-    hipLaunchKernelGGL(k_pw_centres<false>, grid, block, 0, S(stream), d_xyz, fstride, n_sel, d_sel, d_weights,
-                       per_frame, d_centre, d_g);
-  return after_launch("k_pw_centres");
+  return launch_centres("rmsf_pairwise_centres", d_xyz, fstride, n_frames, n_sel, d_sel, d_weights, per_frame,
+                        nullptr, d_centre, d_g, stream);
+}
+
+RMSF_EXPORT int rmsf_pairwise_centres_about(const float *d_xyz, int64_t fstride, int64_t n_frames, int64_t n_sel,
+                                            const int32_t *d_sel, const double *d_weights, const double *d_about,
+                                            double *d_centre, double *d_g, void *stream) {
+  if (!d_xyz || !d_about || !d_centre || !d_g || n_sel < 1 || n_frames < 0 || fstride < 0)
+    return fail(RMSF_EINVAL, "rmsf_pairwise_centres_about: bad arguments");
+  return launch_centres("rmsf_pairwise_centres_about", d_xyz, fstride, n_frames, n_sel, d_sel, d_weights, 0,
+                        d_about, d_centre, d_g, stream);
 }
 
 RMSF_EXPORT size_t rmsf_pairwise_workspace_bytes(int64_t n_frames, int64_t n_sel) {
@@ -372,6 +643,59 @@ RMSF_EXPORT int rmsf_pairwise_rmsd(const float *d_xyz, int64_t fstride, int64_t 
     if (int rc = after_launch("k_pw_fold")) return rc;
   }
   return RMSF_OK;
+}
+
+RMSF_EXPORT size_t rmsf_cross_workspace_bytes(int64_t n_a, int64_t n_b, int64_t n_sel) {
+  if (n_sel < 1 || n_a < 1 || n_b < 1) return 0;
+  return cross_work_doubles(cross_plan(n_a, n_b, n_sel)) * sizeof(double);
+}
+
+RMSF_EXPORT int rmsf_cross_rmsd(const float *d_a, int64_t stride_a, int64_t n_a, const int32_t *d_sel_a,
+                                const double *d_centre_a, const double *d_g_a, const float *d_b, int64_t stride_b,
+                                int64_t n_b, const int32_t *d_sel_b, const double *d_centre_b, const double *d_g_b,
+                                int64_t n_sel, const double *d_weights, double w_total, int superpose,
+                                double cutoff, double *d_out, int64_t ld, void *d_work, size_t work_bytes,
+                                void *stream) {
+  if (!d_a || !d_centre_a || !d_g_a || !d_b || !d_centre_b || !d_g_b || !d_out || n_sel < 1 || n_a < 0 || n_b < 0 ||
+      stride_a < 0 || stride_b < 0 || ld < n_b || !(w_total > 0.0))
+    return fail(RMSF_EINVAL, "rmsf_cross_rmsd: bad arguments");
+  if (n_a == 0 || n_b == 0) return RMSF_OK;
+  const CrossPlan pl = cross_plan(n_a, n_b, n_sel);
+  if (pl.n_pairs == 0 || pl.n_ks > 65535)
+    return fail(RMSF_EINVAL, "rmsf_cross_rmsd: too many frames for one launch");
+  const size_t need = cross_work_doubles(pl) * sizeof(double);
+  if (need && (!d_work || work_bytes < need)) return fail(RMSF_ENOMEM, "rmsf_cross_rmsd: workspace too small");
+  const int direct = pl.n_ks == 1;
+  double *work = static_cast<double *>(d_work);
+  const CrossSide sa{d_a, stride_a, n_a, d_sel_a, d_centre_a, d_g_a};
+  const CrossSide sb{d_b, stride_b, n_b, d_sel_b, d_centre_b, d_g_b};
+  const dim3 grid((unsigned)pl.n_pairs, (unsigned)pl.n_ks), block(kBlock);
+#define CROSS_LAUNCH(G_, W_)                                                                                    \
+  hipLaunchKernelGGL((k_pw_cross_tiles<G_, W_>), grid, block, 0, S(stream), sa, sb, n_sel, d_weights, superpose, \
+                     w_total, cutoff, d_out, ld, work, pl.tiles_b, pl.n_pairs, pl.ks_atoms, direct)
+  const bool gt = d_sel_a != nullptr || d_sel_b != nullptr, wt = d_weights != nullptr;
+  if (gt && wt) CROSS_LAUNCH(true, true);
+  else if (gt) CROSS_LAUNCH(true, false);
+  else if (wt) CROSS_LAUNCH(false, true);
+  else CROSS_LAUNCH(false, false);
+#undef CROSS_LAUNCH
+  if (int rc = after_launch("k_pw_cross_tiles")) return rc;
+  if (!direct) {
+    hipLaunchKernelGGL(k_pw_cross_fold, dim3((unsigned)pl.n_pairs), block, 0, S(stream), work, n_a, n_b, pl.tiles_b,
+                       pl.n_pairs, pl.n_ks, d_g_a, d_g_b, superpose, w_total, cutoff, d_out, ld);
+    if (int rc = after_launch("k_pw_cross_fold")) return rc;
+  }
+  return RMSF_OK;
+}
+
+RMSF_EXPORT int rmsf_row_argmin(const double *d_m, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t *d_idx,
+                                double *d_val, void *stream) {
+  if (!d_m || (!d_idx && !d_val) || n_rows < 0 || n_cols < 1 || ld < n_cols)
+    return fail(RMSF_EINVAL, "rmsf_row_argmin: bad arguments");
+  if (n_rows > INT32_MAX) return fail(RMSF_EINVAL, "rmsf_row_argmin: too many rows for one launch");
+  if (n_rows == 0) return RMSF_OK;
+  hipLaunchKernelGGL(k_row_argmin, dim3((unsigned)n_rows), dim3(kBlock), 0, S(stream), d_m, n_cols, ld, d_idx, d_val);
+  return after_launch("k_row_argmin");
 }
 
 }  // extern "C"

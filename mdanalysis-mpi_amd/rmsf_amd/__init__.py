@@ -15,6 +15,10 @@ Public surface (mirrors the reference's names):
     ``rmsip`` / ``cumulative_overlap`` compare two sets of modes
   * ``DistanceMatrix`` / ``DiffusionMap`` -- the all-pairs RMSD matrix of the frames and
     its diffusion map, named as MDAnalysis.analysis.diffusionmap names them
+  * ``CrossDistanceMatrix`` -- the rectangular RMSD matrix of every frame of one trajectory to
+    every frame of another (or to a set of references) and each frame's nearest reference;
+    ``hausdorff`` / ``discrete_frechet`` -- the path distances of such a matrix, named as
+    MDAnalysis.analysis.psa names them
 """
 from ._lib import RmsfEmptyError, RmsfError, load as load_library
 from .parallel import blocks
@@ -23,7 +27,7 @@ from .moments import second_order_moments
 from .rms import RMSF, Results
 from .eigen import PCAConvergenceError
 from .pca import PCA, cosine_content, cumulative_overlap, pca_from_comoment, rmsip
-from .distances import DiffusionMap, DistanceMatrix
+from .distances import CrossDistanceMatrix, DiffusionMap, DistanceMatrix, discrete_frechet, hausdorff
 
 __all__ = [
     "RMSF",
@@ -36,6 +40,9 @@ __all__ = [
     "PCAConvergenceError",
     "DistanceMatrix",
     "DiffusionMap",
+    "CrossDistanceMatrix",
+    "hausdorff",
+    "discrete_frechet",
     "blocks",
     "second_order_moments",
     "get_rotation_matrix",

@@ -117,6 +117,11 @@ SIGNATURES = {
     "rmsf_pairwise_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "rmsf_pairwise_rmsd": (c_int, [P, c_int64, c_int64, c_int64, P, P, c_double, P, P, c_int, c_double, P, c_int64, P,
                                    c_size_t, P]),
+    "rmsf_pairwise_centres_about": (c_int, [P, c_int64, c_int64, c_int64, P, P, P, P, P, P]),
+    "rmsf_cross_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "rmsf_cross_rmsd": (c_int, [P, c_int64, c_int64, P, P, P, P, c_int64, c_int64, P, P, P, c_int64, P, c_double,
+                                c_int, c_double, P, c_int64, P, c_size_t, P]),
+    "rmsf_row_argmin": (c_int, [P, c_int64, c_int64, c_int64, P, P, P]),
     "rmsf_qcp_batch": (c_int, [P, P, P, c_int64, P, P, P]),
     "rmsf_calc_rmsd_rotational_matrix": (c_int, [P, P, c_int64, P, P, POINTER(c_double)]),
     "rmsf_synth_frames": (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_uint64, P, P]),

@@ -12,10 +12,18 @@ kernel -- no rotation, no 9 F^2 intermediate, every pair once.
 ``DiffusionMap`` is the eigen-decomposition of the diffusion kernel of that
 matrix, on the host (numpy only, like ``pca_from_comoment``).
 
+``CrossDistanceMatrix(a, b).run().results.dist_matrix`` is the rectangular
+F_a x F_b matrix of the RMSDs of every frame of one trajectory to every frame
+of another (or to a set of reference structures), by the same contraction
+over the whole tile rectangle with a second operand of its own;
+``results.nearest`` names each frame's nearest reference.  ``hausdorff`` and
+``discrete_frechet`` are the path-similarity distances of such a matrix, on
+the host, named as ``MDAnalysis.analysis.psa`` names them.
+
 MDAnalysis is not a dependency and is absent where this was written: its
 semantics (``DistanceMatrix``'s metric and cutoff, ``rms.rmsd``'s weights,
-``DiffusionMap``'s kernel and ``transform``) are restated from its published
-documentation, not verified against it.
+``DiffusionMap``'s kernel and ``transform``, ``psa``'s two distances) are
+restated from its published documentation, not verified against it.
 """
 from __future__ import annotations
 
@@ -60,6 +68,63 @@ def _check_n_sel(n_sel: int) -> None:
     if n_sel < 3:
         raise ValueError(f"DistanceMatrix needs at least 3 selected atoms, got {n_sel}: the superposition of fewer "
                          "is degenerate")
+
+
+def _n_sel_hint(x, select, layout: str):
+    """The selection's size where the input shows it without a source."""
+    if hasattr(x, "n_sel"):
+        return int(x.n_sel)
+    if select is not None:
+        return int(np.asarray(select).reshape(-1).size)
+    if isinstance(x, (np.ndarray, torch.Tensor)) and x.ndim == 3:
+        return int(x.shape[2] if layout == "soa" else x.shape[1])
+    if hasattr(x, "universe") and hasattr(x, "n_atoms"):
+        return int(x.n_atoms)
+    return None
+
+
+def _in_place_run(src, fl: FrameList):
+    """(first, step) where the frames of ``fl`` can be read where they lie: a
+    dense HBM tensor and a frame list of one run; None otherwise."""
+    n_frames = len(fl)
+    if isinstance(src, DeviceSource) and src.layout == "fac":
+        runs = list(fl.runs(0, n_frames, n_frames))
+        if len(runs) == 1:
+            first, step, n = runs[0]
+            for f in (first, first + step * (n - 1)):
+                if not src.holds(f):
+                    raise IndexError(f"frame {f} is not resident in this HBM tensor")
+            return first, step
+    return None
+
+
+def resident_frames(eng: Engine, src, fl: FrameList, batch_frames, check):
+    """(keep-alive, ptr, frame stride, device selection) of the frames of
+    ``fl`` at a constant stride: read in place (see ``_in_place_run``), or
+    copied once into a dense [F, n_sel, 3] f32 buffer, batch by batch.
+    ``check(dense_bytes)`` runs before anything is allocated (the callers'
+    MemoryError).  The residency rule of ``DistanceMatrix`` and of either side
+    of ``CrossDistanceMatrix``."""
+    n_frames, n_sel = len(fl), src.n_sel
+    run = _in_place_run(src, fl)
+    if run is not None:
+        first, step = run
+        check(0)
+        return src.traj, src._ptr(first), src.fstride * step, src.sel_dev
+    check(12 * n_frames * n_sel)
+    dense = torch.empty((n_frames, n_sel, 3), dtype=torch.float32, device=eng.device)
+    nb = max(1, min(batch_frames or n_frames, MAX_GATHER))
+    rows = torch.arange(min(nb, n_frames), dtype=torch.int64, device=eng.device)
+    done = 0
+    for b in src.batches(fl, 0, n_frames, nb, eng.stream):
+        if b.pstride:
+            raise NotImplementedError(_PW_PLANES)
+        eng.gather_frames(b.ptr, b.fstride, rows, b.n_frames, n_sel, b.sel, dense[done:done + b.n_frames])
+        b.done()
+        done += b.n_frames
+    if done != n_frames:
+        raise RuntimeError(f"the source yielded {done} of {n_frames} frames")
+    return dense, dense.data_ptr(), 3 * n_sel, None
 
 
 class DistanceMatrix:
@@ -124,17 +189,7 @@ class DistanceMatrix:
 
     # -- what can be refused without a device ------------------------------
     def _n_sel_hint(self):
-        """The selection's size where the input shows it without a source."""
-        x = self._input
-        if hasattr(x, "n_sel"):
-            return int(x.n_sel)
-        if self.select is not None:
-            return int(np.asarray(self.select).reshape(-1).size)
-        if isinstance(x, (np.ndarray, torch.Tensor)) and x.ndim == 3:
-            return int(x.shape[2] if self.layout == "soa" else x.shape[1])
-        if hasattr(x, "universe") and hasattr(x, "n_atoms"):
-            return int(x.n_atoms)
-        return None
+        return _n_sel_hint(self._input, self.select, self.layout)
 
     def _refuse(self) -> None:
         x = self._input
@@ -160,33 +215,9 @@ class DistanceMatrix:
 
     # -- the frames, dense in HBM -------------------------------------------
     def _resident(self, eng: Engine, src, fl: FrameList):
-        """(keep-alive, ptr, frame stride, device selection) of the frames at
-        a constant stride."""
-        n_frames, n_sel = len(fl), src.n_sel
-        if isinstance(src, DeviceSource) and src.layout == "fac":
-            runs = list(fl.runs(0, n_frames, n_frames))
-            if len(runs) == 1:  # read in place
-                first, step, n = runs[0]
-                for f in (first, first + step * (n - 1)):
-                    if not src.holds(f):
-                        raise IndexError(f"frame {f} is not resident in this HBM tensor")
-                check_pairwise_memory(eng, n_frames)
-                return src.traj, src._ptr(first), src.fstride * step, src.sel_dev
-        dense_bytes = 12 * n_frames * n_sel
-        check_pairwise_memory(eng, n_frames, dense_bytes)
-        dense = torch.empty((n_frames, n_sel, 3), dtype=torch.float32, device=eng.device)
-        nb = max(1, min(self.batch_frames or n_frames, MAX_GATHER))
-        rows = torch.arange(min(nb, n_frames), dtype=torch.int64, device=eng.device)
-        done = 0
-        for b in src.batches(fl, 0, n_frames, nb, eng.stream):
-            if b.pstride:
-                raise NotImplementedError(_PW_PLANES)
-            eng.gather_frames(b.ptr, b.fstride, rows, b.n_frames, n_sel, b.sel, dense[done:done + b.n_frames])
-            b.done()
-            done += b.n_frames
-        if done != n_frames:
-            raise RuntimeError(f"the source yielded {done} of {n_frames} frames")
-        return dense, dense.data_ptr(), 3 * n_sel, None
+        n_frames = len(fl)
+        return resident_frames(eng, src, fl, self.batch_frames,
+                               lambda dense_bytes: check_pairwise_memory(eng, n_frames, dense_bytes))
 
     def run(self, start=None, stop=None, step=None, frames=None, **kwargs):
         self._refuse()
@@ -200,8 +231,7 @@ class DistanceMatrix:
             fl = FrameList(src.n_traj, start, stop, step, frames=frames)
             n_frames = len(fl)
             r = self.results
-            r.frames = (np.asarray(fl.idx, dtype=np.int64).copy() if fl.idx is not None
-                        else np.arange(fl.r.start, fl.r.stop, fl.r.step, dtype=np.int64))
+            r.frames = _frame_rows(fl)
             r.n_frames = self.n_frames = n_frames
             if n_frames == 0:
                 r.dist_matrix = np.zeros((0, 0))
@@ -223,6 +253,209 @@ class DistanceMatrix:
     @property
     def dist_matrix(self):
         return self.results.dist_matrix
+
+
+def _frame_rows(fl: FrameList) -> np.ndarray:
+    return (np.asarray(fl.idx, dtype=np.int64).copy() if fl.idx is not None
+            else np.arange(fl.r.start, fl.r.stop, fl.r.step, dtype=np.int64))
+
+
+def _one_frame(x):
+    """A 2-D array ([n_atoms, 3], or [3, n_atoms] planes) is one frame."""
+    if isinstance(x, (np.ndarray, torch.Tensor)) and x.ndim == 2:
+        return x[None]
+    return x
+
+
+class CrossDistanceMatrix:
+    """The rectangular RMSD matrix of two trajectories,
+    ``results.dist_matrix[i, j] = RMSD(A_i, B_j)`` (host f64 [F_a, F_b]): the
+    RMSD of every frame to a set of reference structures, the 2-D RMSD plot
+    between two runs, the input of ``hausdorff`` and ``discrete_frechet``.
+    Only the F_a x F_b pairs asked for are computed (csrc/pairwise.hip,
+    ``k_pw_cross_tiles``), each once.
+
+    Parameters
+    ----------
+    a, b : as ``DistanceMatrix``'s input, independently of each other (an HBM
+        tensor read in place against a host array or an ``.xtc`` path, ...).
+        A 2-D [n_atoms, 3] array is one frame.
+    select, select_b : array of int, optional
+        The atoms of A and of B (``select_b`` defaults to ``select``); atom k
+        of one is paired with atom k of the other, so both must have the same
+        length, at least 3.  The frames of A and B may differ in size.
+    weights : None | "mass" | array [n_sel]
+        One weight per selected atom, shared by both sides; "mass": the masses
+        of A's AtomGroup.
+    superposition, cutoff : as ``DistanceMatrix``.
+    layout, layout_b : "fac" | "soa"
+        As ``DistanceMatrix``'s ``layout``, per side (``layout_b`` defaults to
+        ``layout``).
+
+    ``run(start, stop, step, frames=None, frames_b=None)``: the frame
+    arguments apply to A; B is used whole, or restricted to ``frames_b``.
+    ``results.frames`` / ``results.frames_b`` are the trajectory indices of the
+    rows / columns, ``results.n_frames`` / ``results.n_frames_b`` their counts.
+    ``results.nearest`` (int64 [F_a]) is the column of each row's least
+    distance -- the lowest such column where several are equal, which happens:
+    the cutoff writes exact zeros and references can be duplicated -- and
+    ``results.nearest_dist`` (f64 [F_a]) that distance; both are found on the
+    device before the matrix is copied back (``rmsf_row_argmin``).  With no
+    frames on either side the matrix is empty, ``nearest`` is -1 and
+    ``nearest_dist`` NaN.
+
+    Residency, per side, as ``DistanceMatrix``; a result plus dense copies over
+    half the free HBM is a MemoryError before anything is launched.  One
+    device per process; HBM-resident planes are refused.
+    """
+
+    def __init__(self, a, b, *, select=None, select_b=None, weights=None, superposition: bool = True,
+                 cutoff: float = 1e-5, layout: str = "fac", layout_b: str | None = None, device=None,
+                 batch_frames: int | None = None, gpus=None):
+        layout_b = layout if layout_b is None else layout_b
+        for lay in (layout, layout_b):
+            if lay not in ("fac", "soa"):
+                raise ValueError(f"layout must be 'fac' or 'soa', got {lay!r}")
+        self._a, self._b = _one_frame(a), _one_frame(b)
+        self.select = select
+        self.select_b = select if select_b is None else select_b
+        self.weights = weights
+        self.superposition = bool(superposition)
+        self.cutoff = float(cutoff)
+        self.layout, self.layout_b = layout, layout_b
+        self.device = device
+        self.batch_frames = batch_frames
+        self.gpus = gpus
+        self.results = Results()
+        self.n_frames = self.n_frames_b = None
+
+    def _refuse(self) -> None:
+        sides = ((self._a, self.select, self.layout), (self._b, self.select_b, self.layout_b))
+        if self.gpus is not None or any(isinstance(x, (list, tuple)) for x, _, _ in sides):
+            raise NotImplementedError("CrossDistanceMatrix runs on one device per process: not with gpus= or a list "
+                                      "of shards")
+        for x, _, lay in sides:
+            if (isinstance(x, DeviceSource) and x.layout == "soa") or (
+                    isinstance(x, torch.Tensor) and x.device.type == "cuda" and lay == "soa"):
+                raise NotImplementedError(_PW_PLANES)
+        if isinstance(self.weights, str):
+            if self.weights != "mass":
+                raise ValueError(f'weights must be None, "mass" or an array, got {self.weights!r}')
+            if not hasattr(self._a, "masses"):
+                raise ValueError('weights="mass" needs an AtomGroup as A; pass the masses as an array')
+        hints = [_n_sel_hint(x, s, lay) for x, s, lay in sides]
+        if None not in hints and hints[0] != hints[1]:
+            raise ValueError(f"the selections of A and B must have the same length, got {hints[0]} and {hints[1]}")
+        for n_sel in hints:
+            if n_sel is not None:
+                _check_n_sel(n_sel)
+                if self.weights is not None and not isinstance(self.weights, str):
+                    _check_weights(self.weights, n_sel)
+        if parallel.world()[1] > 1:
+            raise NotImplementedError("CrossDistanceMatrix runs on one device per process: not under "
+                                      "torch.distributed with more than one rank")
+
+    def run(self, start=None, stop=None, step=None, frames=None, frames_b=None, **kwargs):
+        self._refuse()
+        eng = Engine(self.device)
+        with torch.cuda.device(eng.device):
+            src_a, masses = make_source(self._a, select=self.select, align=None, batch_frames=self.batch_frames,
+                                        layout=self.layout, group_masses=isinstance(self.weights, str))
+            src_b, _ = make_source(self._b, select=self.select_b, align=None, batch_frames=self.batch_frames,
+                                   layout=self.layout_b, group_masses=False)
+            n_sel = src_a.n_sel
+            if src_b.n_sel != n_sel:
+                raise ValueError(f"the selections of A and B must have the same length, got {n_sel} and "
+                                 f"{src_b.n_sel}")
+            _check_n_sel(n_sel)
+            w = _check_weights(masses if isinstance(self.weights, str) else self.weights, n_sel)
+            fl_a = FrameList(src_a.n_traj, start, stop, step, frames=frames)
+            fl_b = FrameList(src_b.n_traj, frames=frames_b)
+            n_a, n_b = len(fl_a), len(fl_b)
+            r = self.results
+            r.frames, r.frames_b = _frame_rows(fl_a), _frame_rows(fl_b)
+            r.n_frames = self.n_frames = n_a
+            r.n_frames_b = self.n_frames_b = n_b
+            if n_a == 0 or n_b == 0:
+                r.dist_matrix = np.zeros((n_a, n_b))
+                r.nearest = np.full(n_a, -1, dtype=np.int64)
+                r.nearest_dist = np.full(n_a, np.nan)
+                return self
+            # the result and both dense copies, before anything is allocated
+            dense = sum(0 if _in_place_run(s, fl) is not None else 12 * len(fl) * n_sel
+                        for s, fl in ((src_a, fl_a), (src_b, fl_b)))
+            need = 8 * n_a * n_b
+            free = torch.cuda.mem_get_info(eng.device)[0]
+            if need + dense > free // 2:
+                raise MemoryError(f"CrossDistanceMatrix: the [{n_a}, {n_b}] f64 matrix needs {need} bytes"
+                                  + (f" and the dense copies of the selected rows {dense} bytes" if dense else "")
+                                  + f", over half of the {free} bytes of free HBM")
+            keep_a, ptr_a, stride_a, sel_a = resident_frames(eng, src_a, fl_a, self.batch_frames, lambda _: None)
+            keep_b, ptr_b, stride_b, sel_b = resident_frames(eng, src_b, fl_b, self.batch_frames, lambda _: None)
+            w_dev = None if w is None else torch.tensor(w, device=eng.device)
+            w_total = float(n_sel) if w is None else float(w.sum())
+            if self.superposition:
+                centre_a, g_a = eng.pairwise_centres(ptr_a, stride_a, n_a, n_sel, sel_a, w_dev, True)
+                centre_b, g_b = eng.pairwise_centres(ptr_b, stride_b, n_b, n_sel, sel_b, w_dev, True)
+            else:  # one common shift: the centre of A's first frame
+                centre_a, g_a = eng.pairwise_centres(ptr_a, stride_a, n_a, n_sel, sel_a, w_dev, False)
+                centre_b, g_b = eng.pairwise_centres_about(ptr_b, stride_b, n_b, n_sel, sel_b, w_dev, centre_a)
+            work_bytes = eng.cross_workspace_bytes(n_a, n_b, n_sel)
+            work = eng.empty(work_bytes // 8) if work_bytes else None
+            out = eng.empty(n_a, n_b)
+            eng.cross_rmsd(ptr_a, stride_a, n_a, sel_a, centre_a, g_a, ptr_b, stride_b, n_b, sel_b, centre_b, g_b,
+                           n_sel, w_dev, w_total, out, superpose=self.superposition, cutoff=self.cutoff, work=work)
+            idx, val = eng.row_argmin(out)
+            torch.cuda.current_stream(eng.device).synchronize()
+            r.dist_matrix = out.cpu().numpy()
+            r.nearest, r.nearest_dist = idx.cpu().numpy(), val.cpu().numpy()
+            del keep_a, keep_b
+        return self
+
+    @property
+    def dist_matrix(self):
+        return self.results.dist_matrix
+
+
+def _cross_matrix(d) -> np.ndarray:
+    d = np.asarray(d, dtype=np.float64)
+    if d.ndim != 2 or d.size == 0:
+        raise ValueError("a cross distance matrix [F_a, F_b] with at least one frame a side is needed")
+    return d
+
+
+def hausdorff(d) -> float:
+    """The Hausdorff distance of two paths from their cross matrix ``d[i, j]``
+    (``CrossDistanceMatrix``'s ``dist_matrix``): the largest distance of a
+    frame of either path to the nearest frame of the other, ``max(d.min(1)
+    .max(), d.min(0).max())``.  Named as ``MDAnalysis.analysis.psa.hausdorff``;
+    its semantics are restated from its documentation, not verified against
+    it.  Host only, numpy only."""
+    d = _cross_matrix(d)
+    return float(max(d.min(axis=1).max(), d.min(axis=0).max()))
+
+
+def discrete_frechet(d) -> float:
+    """The discrete Frechet distance of two paths from their cross matrix: the
+    last entry of the coupling recurrence ``c[i, j] = max(d[i, j], min(c[i-1,
+    j], c[i-1, j-1], c[i, j-1]))`` (Eiter and Mannila 1994), evaluated one
+    anti-diagonal at a time -- the entries of an anti-diagonal depend only on
+    the two before it, so F_a + F_b - 1 vector steps replace the F_a F_b scalar
+    ones.  Only selects and compares entries of ``d``: the result is one of
+    them.  Named as ``MDAnalysis.analysis.psa.discrete_frechet``; its semantics
+    are restated from its documentation, not verified against it.  Host only,
+    numpy only."""
+    d = _cross_matrix(d)
+    n, m = d.shape
+    # c with a border of +inf: row 0 and column 0 stand for "no predecessor";
+    # the corner is -inf so that c[1, 1] = d[0, 0]
+    c = np.full((n + 1, m + 1), np.inf)
+    c[0, 0] = -np.inf
+    for k in range(2, n + m + 1):
+        i = np.arange(max(1, k - m), min(n, k - 1) + 1)
+        j = k - i
+        c[i, j] = np.maximum(d[i - 1, j - 1], np.minimum(np.minimum(c[i - 1, j], c[i - 1, j - 1]), c[i, j - 1]))
+    return float(c[n, m])
 
 
 class DiffusionMap:

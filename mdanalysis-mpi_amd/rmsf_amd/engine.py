@@ -537,6 +537,59 @@ class Engine:
              centre.data_ptr(), g.data_ptr(), int(bool(superpose)), float(cutoff), out.data_ptr(), out.stride(0),
              _ptr(work), 0 if work is None else work.numel() * work.element_size(), self.stream)
 
+    # -- cross RMSD matrix: frames of A against frames of B (csrc/pairwise.hip) --
+    def pairwise_centres_about(self, xyz_ptr: int, fstride: int, n_frames: int, n_sel: int, sel, weights,
+                               about: torch.Tensor):
+        """pairwise_centres(per_frame=False) about a centre found elsewhere:
+        ``about`` (f64, its first three entries) for every frame, and G about
+        it (rmsf_pairwise_centres_about) -- the common shift of the second side
+        of a cross matrix without superposition."""
+        if about.dtype != F64 or about.numel() < 3 or not about.is_contiguous():
+            raise ValueError("pairwise_centres_about: buffer sizes")
+        centre, g = self.empty(n_frames, 3), self.empty(n_frames)
+        call("rmsf_pairwise_centres_about", xyz_ptr, fstride, n_frames, n_sel, _ptr(sel), _ptr(weights),
+             about.data_ptr(), centre.data_ptr(), g.data_ptr(), self.stream)
+        return centre, g
+
+    def cross_workspace_bytes(self, n_a: int, n_b: int, n_sel: int) -> int:
+        return int(self.lib.rmsf_cross_workspace_bytes(n_a, n_b, n_sel))
+
+    def cross_rmsd(self, a_ptr: int, stride_a: int, n_a: int, sel_a, centre_a: torch.Tensor, g_a: torch.Tensor,
+                   b_ptr: int, stride_b: int, n_b: int, sel_b, centre_b: torch.Tensor, g_b: torch.Tensor,
+                   n_sel: int, weights, w_total: float, out: torch.Tensor, superpose: bool = True,
+                   cutoff: float = 0.0, work: torch.Tensor | None = None) -> None:
+        """out[i, j] = the RMSD of frame i of A and frame j of B (minimal over
+        rotations when ``superpose``), 0 where <= ``cutoff``, on the f64 matrix
+        cores (rmsf_cross_rmsd).  ``centre_*``, ``g_*``: pairwise_centres' of
+        each side (superposed), or pairwise_centres(per_frame=False) of A and
+        pairwise_centres_about(A's centre) of B (plain).  ``work``: f64 scratch
+        of at least cross_workspace_bytes(n_a, n_b, n_sel) bytes (None when 0)."""
+        sides = ((centre_a, g_a, n_a), (centre_b, g_b, n_b))
+        if (out.dtype != F64 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n_a or out.shape[1] < n_b
+                or any(c.dtype != F64 or g.dtype != F64 or c.numel() < 3 * n or g.numel() < n
+                       or not c.is_contiguous() for c, g, n in sides)):
+            raise ValueError("cross_rmsd: buffer sizes")
+        call("rmsf_cross_rmsd", a_ptr, stride_a, n_a, _ptr(sel_a), centre_a.data_ptr(), g_a.data_ptr(),
+             b_ptr, stride_b, n_b, _ptr(sel_b), centre_b.data_ptr(), g_b.data_ptr(), n_sel, _ptr(weights),
+             float(w_total), int(bool(superpose)), float(cutoff), out.data_ptr(), out.stride(0),
+             _ptr(work), 0 if work is None else work.numel() * work.element_size(), self.stream)
+
+    def row_argmin(self, m: torch.Tensor, n_rows: int | None = None, n_cols: int | None = None):
+        """(int64 [n_rows], f64 [n_rows]): of every row of ``m[:n_rows,
+        :n_cols]`` the lowest column holding its least entry, and that entry
+        (rmsf_row_argmin; numpy.argmin's tie rule, which torch.min does not
+        promise)."""
+        n_rows = m.shape[0] if n_rows is None else n_rows
+        n_cols = m.shape[1] if n_cols is None else n_cols
+        if (m.dtype != F64 or m.dim() != 2 or m.stride(1) != 1 or m.shape[0] < n_rows or m.shape[1] < n_cols
+                or n_cols < 1):
+            raise ValueError("row_argmin: buffer sizes")
+        idx = torch.empty(n_rows, dtype=torch.int64, device=self.device)
+        val = self.empty(n_rows)
+        call("rmsf_row_argmin", m.data_ptr(), n_rows, n_cols, m.stride(0), idx.data_ptr(), val.data_ptr(),
+             self.stream)
+        return idx, val
+
     def qcp_batch(self, A: torch.Tensor, E0: torch.Tensor, N: torch.Tensor):
         n = A.shape[0]
         rot = self.empty(n, 9)

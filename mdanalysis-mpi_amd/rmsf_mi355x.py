@@ -57,6 +57,13 @@ def main(argv=None) -> int:
     ap.add_argument("--dist-matrix", default=None, metavar="OUT.npy",
                     help="also write the all-pairs RMSD matrix of the selected atoms' frames, f64 [F, F] "
                          "(rmsf_amd.DistanceMatrix; each pair superposed unless --align none; one process only)")
+    ap.add_argument("--cross-rmsd", default=None, metavar="OUT.npy",
+                    help="also write the RMSD of every frame of the trajectory to every frame of --cross-with, "
+                         "f64 [F, F_b] (rmsf_amd.CrossDistanceMatrix; each pair superposed unless --align none; "
+                         "one process only; not with --synthetic)")
+    ap.add_argument("--cross-with", default=None, metavar="TRAJ",
+                    help="--cross-rmsd: the second trajectory (or reference structures), of the same topology and "
+                         "selection")
     ap.add_argument("--pca-transform", default=None, metavar="OUT.npy",
                     help="also run rmsf_amd.PCA on the same input with --align and write the projection of the "
                          "frames on its components, f64 [F, K] (PCA.transform; one process only)")
@@ -77,6 +84,12 @@ def main(argv=None) -> int:
         ap.error(f"--pca-solver {a.pca_solver} needs --n-components")
     if a.dist_matrix and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--dist-matrix runs in one process (no torch.distributed launch)")
+    if bool(a.cross_rmsd) != bool(a.cross_with):
+        ap.error("--cross-rmsd OUT.npy and --cross-with TRAJ go together")
+    if a.cross_rmsd and a.synthetic:
+        ap.error("--cross-rmsd needs --topology/--trajectory")
+    if a.cross_rmsd and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--cross-rmsd runs in one process (no torch.distributed launch)")
     if a.covariance and a.merge == "scatter":
         ap.error("--covariance needs --merge root or all")
     if a.exact and (a.align != "none" or a.merge == "scatter"):
@@ -102,6 +115,7 @@ def main(argv=None) -> int:
     cov_kw = {"covariance": True} if a.covariance else {}
     cov = None
     dm_input, dm_kw = None, {}   # what --dist-matrix reads: the RMSF run's own input
+    cross_b = None               # what --cross-with names, read as the input is
     if a.synthetic:
         n_atoms, n_frames = a.synthetic
         eng = Engine()
@@ -131,6 +145,8 @@ def main(argv=None) -> int:
                            merge_order=a.merge_order, **cov_kw).run().results
             rmsf, cov = results.rmsf, (results.covariance if a.covariance else None)
             dm_input = ag
+            if a.cross_with:
+                cross_b = mda.Universe(a.topology, a.cross_with).select_atoms(a.select)
         else:
             # native fallback: GRO or PSF topology + selection subset; XTC, DCD (or
             # multi-frame GRO) trajectory.  PSF masses (GRO: masses guessed from
@@ -151,11 +167,20 @@ def main(argv=None) -> int:
                            merge_order=a.merge_order, **cov_kw).run().results
             rmsf, cov = results.rmsf, (results.covariance if a.covariance else None)
             dm_input, dm_kw = traj, {"select": sel, "weights": masses}
+            if a.cross_with:
+                cross_b = (a.cross_with if a.cross_with.lower().endswith((".xtc", ".dcd"))
+                           else GroTopology(a.cross_with).frames)
     if a.dist_matrix:
         from rmsf_amd import DistanceMatrix
         dm = DistanceMatrix(dm_input, superposition=align is not None, **dm_kw).run().results
         print(f"RMSD matrix over {dm.n_frames} frames: max {dm.dist_matrix.max():.6f} A", flush=True)
         np.save(a.dist_matrix, dm.dist_matrix)
+    if a.cross_rmsd:
+        from rmsf_amd import CrossDistanceMatrix
+        cm = CrossDistanceMatrix(dm_input, cross_b, superposition=align is not None, **dm_kw).run().results
+        print(f"cross RMSD matrix, {cm.n_frames} x {cm.n_frames_b} frames: max {cm.dist_matrix.max():.6f} A, "
+              f"largest distance to the nearest frame of --cross-with {cm.nearest_dist.max():.6f} A", flush=True)
+        np.save(a.cross_rmsd, cm.dist_matrix)
     if a.pca_transform:
         from rmsf_amd import PCA
         pca_kw = {"select": dm_kw["select"], "masses": dm_kw["weights"]} if dm_kw else {}
