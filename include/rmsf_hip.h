@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RMSF_ABI_VERSION 2
+#define RMSF_ABI_VERSION 3
 
 #define RMSF_OK 0
 #define RMSF_EINVAL (-1)   /* bad argument (shape, null pointer, size)      */
@@ -50,6 +50,10 @@ extern "C" {
 /* longest frame tile one rmsf_accumulate split may hold (Welford
  * coefficient table); n_splits >= ceil(n_frames / RMSF_MAX_SPLIT_FRAMES)    */
 #define RMSF_MAX_SPLIT_FRAMES 4096
+/* how a pair's lambda was found (rmsf_pair_lambda_host)                      */
+#define RMSF_PAIR_NEWTON 0 /* Newton's iteration, at a simple root            */
+#define RMSF_PAIR_JACOBI 1 /* largest eigenvalue of the 4 x 4 key matrix       */
+#define RMSF_PAIR_ZERO 2   /* E0 <= 0 (two all-zero frames) or NaN: lambda = E0 */
 /* Size of the reference record written by rmsf_reference_setup():
  * [0..15]  ref_com[3], sum_r[3] (= sum of centred ref coords),
  *          G_ref (= sum |r|^2), total mass, n_sel, pad[7]
@@ -721,7 +725,17 @@ int rmsf_pairwise_rmsd(const float *d_xyz, int64_t frame_stride,
  * least entry (d_val[n_rows], may be NULL) and the lowest column holding it
  * (d_idx[n_rows], may be NULL) -- strict comparisons in a fixed order, so
  * equal minima (exact zeros below the cutoff, duplicated references) resolve
- * to the first; NaN entries are not ordered.                                */
+ * to the first.  A NaN is below every number, as for numpy.argmin: a row
+ * that holds one returns its first NaN's column and that NaN.
+ * The lambda of a pair (superpose = 1): Newton's iteration on the QCP
+ * quartic from E0, as qcprot's; where it has not met its stopping rule or
+ * the quartic's slope there is below lambda^3 / 16 -- a double or nearly
+ * double largest root: collinear, planar or collapsed frames, reflections of
+ * symmetric structures -- the largest eigenvalue of the 4 x 4 key matrix by
+ * cyclic Jacobi instead.  d^2 is then
+ * within 1e-12 (G_i + G_j) / (2 w_total) of the exact value for every pair.
+ * A non-finite coordinate makes its own frame's row and column NaN and
+ * changes no other entry.                                                   */
 int rmsf_pairwise_centres_about(const float *d_xyz, int64_t frame_stride,
                                 int64_t n_frames, int64_t n_sel,
                                 const int32_t *d_sel, const double *d_weights,
@@ -738,6 +752,13 @@ int rmsf_cross_rmsd(const float *d_a, int64_t stride_a, int64_t n_a,
                     void *d_work, size_t work_bytes, void *stream);
 int rmsf_row_argmin(const double *d_m, int64_t n_rows, int64_t n_cols,
                     int64_t ld, int64_t *d_idx, double *d_val, void *stream);
+
+/* The epilogue's lambda on the host, the device's own code (no device is
+ * touched): for each of n pairs, h_A[9 k..] (row-major A_ij) and h_E0[k] give
+ * h_lambda[k] and, when h_path is not NULL, the RMSF_PAIR_* way it was found
+ * in h_path[k].                                                             */
+int rmsf_pair_lambda_host(const double *h_A, const double *h_E0, int64_t n,
+                          double *h_lambda, int32_t *h_path);
 
 /* ---- qcprot.CalcRMSDRotationalMatrix (RMSF.py:48) --------------------------
  * Batched QCP on device: A[n][9], E0[n], atom counts N[n] -> rot[n][9],

@@ -24,8 +24,10 @@
 //                   lane's nine accumulators hold the nine entries of A_ij of
 //                   one frame pair per register.
 //   * k_pw_fold     the split-K partials, summed in atom-range order.
-//   * pair_epilogue lambda by Newton's iteration (or the trace, without
-//                   superposition), the cutoff, the store and its mirror.
+//   * pair_epilogue lambda by Newton's iteration, by Jacobi on the key matrix
+//                   where the largest root is not simple (or the trace,
+//                   without superposition), the cutoff, the store and its
+//                   mirror.
 //
 // The rectangle d[i, j] = RMSD(A_i, B_j) of two trajectories is the same
 // contraction with a second operand of its own (base, stride, selection,
@@ -36,7 +38,8 @@
 //                       tile and carries the weight.
 //   * k_pw_cross_fold   its split-K partials, summed in atom-range order.
 //   * cross_epilogue    pair_epilogue without the mirror: one store a pair.
-//   * k_row_argmin      one workgroup per row: the first least entry.
+//   * k_row_argmin      one workgroup per row: the first least entry, a NaN
+//                       below every number.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -143,6 +146,24 @@ __global__ __launch_bounds__(kBlock) void k_pw_centres(const float *__restrict__
   }
 }
 
+// The distance of one pair from its A_ij and the two frames' G: lambda as
+// pair_lambda finds it (rmsf_device.h: Newton's iteration as in qcp_solve,
+// the key matrix' largest eigenvalue where the largest root is not simple),
+// or the trace without superposition; then the cutoff.
+__device__ __forceinline__ double pair_distance(const double *A, double gi, double gj, int superpose,
+                                                double w_total, double cutoff) {
+  double d;
+  if (superpose) {
+    const double E0 = (gi + gj) * 0.5;
+    int path;
+    const double l = pair_lambda(A, E0, &path);
+    d = sqrt(fabs(2.0 * (E0 - l)) / w_total);
+  } else {
+    d = sqrt(fabs(gi + gj - 2.0 * (A[0] + A[4] + A[8])) / w_total);
+  }
+  return d <= cutoff ? 0.0 : d;
+}
+
 // Thread tid owns the frame pair (fi = tid >> 4 of tile I, fj = tid & 15 of
 // tile J) and its A_ij.  Pairs j > i are computed; each value goes to [i, j]
 // and, through LDS so that both stores run along rows, to [j, i]; the
@@ -156,19 +177,7 @@ __device__ __forceinline__ void pair_epilogue(const double *A, int64_t I, int64_
   const int64_t i = kTF * I + fi, j = kTF * J + fj;
   const bool in = i < n_frames && j < n_frames;
   double d = 0.0;
-  if (in && j > i) {
-    const double gi = g[i], gj = g[j];
-    const double E0 = (gi + gj) * 0.5;
-    if (superpose) {
-      // lambda as qcp_solve finds it (rmsf_device.h), without the rotation
-      // (two all-zero frames: the quartic is 0 / 0; their distance is 0)
-      const double l = E0 > 0.0 || E0 != E0 ? qcp_lambda(A, E0) : E0;
-      d = sqrt(fabs(2.0 * (E0 - l)) / w_total);
-    } else {
-      d = sqrt(fabs(gi + gj - 2.0 * (A[0] + A[4] + A[8])) / w_total);
-    }
-    if (d <= cutoff) d = 0.0;
-  }
+  if (in && j > i) d = pair_distance(A, g[i], g[j], superpose, w_total, cutoff);
   if (I == J) {
     // the tile is its own mirror image: the upper half fills both
     if (fj > fi) sd[fi][fj] = d, sd[fj][fi] = d;
@@ -383,18 +392,7 @@ __device__ __forceinline__ void cross_epilogue(const double *A, int64_t I, int64
   const int tid = threadIdx.x;
   const int64_t i = kTF * I + (tid >> 4), j = kTF * J + (tid & 15);
   if (i >= n_a || j >= n_b) return;
-  const double gi = g_a[i], gj = g_b[j];
-  const double E0 = (gi + gj) * 0.5;
-  double d;
-  if (superpose) {
-    // (two all-zero frames: the quartic is 0 / 0; their distance is 0)
-    const double l = E0 > 0.0 || E0 != E0 ? qcp_lambda(A, E0) : E0;
-    d = sqrt(fabs(2.0 * (E0 - l)) / w_total);
-  } else {
-    d = sqrt(fabs(gi + gj - 2.0 * (A[0] + A[4] + A[8])) / w_total);
-  }
-  if (d <= cutoff) d = 0.0;
-  out[i * ld + j] = d;
+  out[i * ld + j] = pair_distance(A, g_a[i], g_b[j], superpose, w_total, cutoff);
 }
 
 // k_pw_tiles over the tile rectangle, each operand with a side of its own:
@@ -535,7 +533,13 @@ __global__ __launch_bounds__(kBlock) void k_pw_cross_fold(const double *__restri
 // lowest column.  Thread t scans columns t, t + 256, ... in order with a
 // strict <, so it keeps the first of equal values; the threads are then
 // joined by a halving tree that prefers the lower column among equal values --
-// the result is the same as one left-to-right scan.
+// the result is the same as one left-to-right scan.  A NaN counts as below
+// every number and equal to another NaN (numpy.argmin's order): a row that
+// holds one returns its first NaN.
+__device__ __forceinline__ bool argmin_below(double v, double than) {
+  return v < than || (v != v && than == than);
+}
+
 __global__ __launch_bounds__(kBlock) void k_row_argmin(const double *__restrict__ m, int64_t n_cols, int64_t ld,
                                                        int64_t *__restrict__ idx, double *__restrict__ val) {
   __shared__ double sv[kBlock];
@@ -547,7 +551,7 @@ __global__ __launch_bounds__(kBlock) void k_row_argmin(const double *__restrict_
   if (tid < n_cols) bv = row[tid], bi = tid;
   for (int64_t c = (int64_t)tid + kBlock; c < n_cols; c += kBlock) {
     const double v = row[c];
-    if (v < bv) bv = v, bi = c;
+    if (argmin_below(v, bv)) bv = v, bi = c;
   }
   sv[tid] = bv, si[tid] = bi;
   __syncthreads();
@@ -555,7 +559,9 @@ __global__ __launch_bounds__(kBlock) void k_row_argmin(const double *__restrict_
     if (tid < s) {
       const double ov = sv[tid + s];
       const int64_t oi = si[tid + s];
-      if (ov < sv[tid] || (ov == sv[tid] && oi < si[tid])) sv[tid] = ov, si[tid] = oi;
+      const double mv = sv[tid];
+      // (neither below the other: equal, or both NaN)
+      if (argmin_below(ov, mv) || (!argmin_below(mv, ov) && oi < si[tid])) sv[tid] = ov, si[tid] = oi;
     }
     __syncthreads();
   }
@@ -696,6 +702,17 @@ RMSF_EXPORT int rmsf_row_argmin(const double *d_m, int64_t n_rows, int64_t n_col
   if (n_rows == 0) return RMSF_OK;
   hipLaunchKernelGGL(k_row_argmin, dim3((unsigned)n_rows), dim3(kBlock), 0, S(stream), d_m, n_cols, ld, d_idx, d_val);
   return after_launch("k_row_argmin");
+}
+
+RMSF_EXPORT int rmsf_pair_lambda_host(const double *h_A, const double *h_E0, int64_t n, double *h_lambda,
+                                      int32_t *h_path) {
+  if (!h_A || !h_E0 || !h_lambda || n < 0) return fail(RMSF_EINVAL, "rmsf_pair_lambda_host: bad arguments");
+  for (int64_t k = 0; k < n; ++k) {
+    int path;
+    h_lambda[k] = pair_lambda(h_A + 9 * k, h_E0[k], &path);
+    if (h_path) h_path[k] = path;
+  }
+  return RMSF_OK;
 }
 
 }  // extern "C"

@@ -45,8 +45,10 @@ __device__ __forceinline__ void apply_xform(float &x, float &y, float &z, const 
 // SURVEY.md Appendix A.2-A.3 gives the exact sequence followed here.
 //
 // The largest root of the QCP quartic: the coefficients, Newton's iteration
-// from lambda = E0 (an upper bound) and its stopping rule.
-__host__ __device__ inline double qcp_lambda(const double *A, double E0) {
+// from lambda = E0 (an upper bound) and its stopping rule.  *met: the rule
+// fired within the 50 steps; *slope: the quartic's derivative at the last
+// point it was evaluated at (the last step's denominator).
+__host__ __device__ inline double qcp_newton(const double *A, double E0, bool *met, double *slope) {
   const double Sxx = A[0], Sxy = A[1], Sxz = A[2];
   const double Syx = A[3], Syy = A[4], Syz = A[5];
   const double Szx = A[6], Szy = A[7], Szz = A[8];
@@ -79,17 +81,134 @@ __host__ __device__ inline double qcp_lambda(const double *A, double E0) {
       (+(SxypSyx) * (SyzmSzy) + (SxzmSzx) * (SxxmSyy - Szz)) *
           (-(SxymSyx) * (SyzpSzy) + (SxzmSzx) * (SxxpSyy - Szz));
 
-  double l = E0;
+  double l = E0, den = 0.0;
+  bool ok = false;
   for (int i = 0; i < 50; ++i) {
     const double old = l;
     const double x2 = l * l;
     const double b = (x2 + C2) * l;
     const double a = b + C1;
-    const double delta = (a * l + C0) / (2.0 * x2 * l + b + a);
+    den = 2.0 * x2 * l + b + a;
+    const double delta = (a * l + C0) / den;
     l -= delta;
-    if (fabs(l - old) < fabs(1e-11 * l)) break;
+    if (fabs(l - old) < fabs(1e-11 * l)) {
+      ok = true;
+      break;
+    }
   }
+  *met = ok;
+  *slope = den;
   return l;
+}
+
+// qcprot's lambda: whatever Newton's iteration ends at.
+__host__ __device__ inline double qcp_lambda(const double *A, double E0) {
+  bool met;
+  double slope;
+  return qcp_newton(A, E0, &met, &slope);
+}
+
+// ---------------------------------------------------------------------------
+// lambda for the RMSD matrices (pairwise.hip), where only the distance is
+// wanted and the pairs are whatever the trajectory holds: mirror images,
+// collinear, planar or collapsed frames, symmetric structures.
+//
+// With s0 >= s1 >= s2 the singular values of A and sigma the sign of det A,
+// the quartic's roots are s0 + s1 + sigma s2 (the largest, lambda), s0 - s1 -
+// sigma s2, -s0 + s1 - sigma s2 and -s0 - s1 + sigma s2.  Its value P is
+// computed to some tens of eps lambda^4 at the best, so the root Newton can
+// reach is off by that over the slope P'(lambda) = (lambda - l2)(lambda - l3)
+// (lambda - l4).  For a simple root the slope is of the order of lambda^3 and
+// the last step, below 1e-11 lambda, leaves that step's square.  Where the two
+// largest roots nearly meet (s1 + sigma s2 ~ 0: atoms on a line, a collapsed
+// frame, a planar frame against its mirror image, a reflection of a structure
+// with s0 = s1 = s2) the slope vanishes: the iteration converges linearly,
+// the residual is rounding noise, and the rule fires on that noise -- on the
+// first step for two nearly equal frames -- or never.
+//
+// So Newton's lambda is kept where the rule fired and the slope is at least
+// lambda^3 / 16: P is a sum of some twenty products bounded by |A|_F^4 <= 9
+// lambda^4, its error below 270 eps lambda^4 = 3e-14 lambda^4, the root's below
+// 16 x 3e-14 lambda = 5e-13 lambda, that is 1e-12 E0 in 2 (E0 - lambda).
+// Pairs of conformations of one molecule have slopes of 0.7 to 2.4 lambda^3
+// and keep qcprot's bits.  Every other pair takes lambda as what it is, the
+// largest eigenvalue of the symmetric traceless 4 x 4 key matrix, by cyclic
+// Jacobi, whose error is a few eps |K| whatever the gaps are.
+constexpr double kPairSlope = 0.0625;
+
+// One Jacobi rotation in the (P, Q) plane of the symmetric k (both triangles
+// kept); the indices are template arguments so that k stays in registers.
+template <int P, int Q>
+__host__ __device__ inline void jacobi_rotate(double (&k)[4][4]) {
+  const double apq = k[P][Q];
+  if (apq == 0.0) return;
+  const double theta = (k[Q][Q] - k[P][P]) / (2.0 * apq);
+  // (theta^2 may overflow to inf: t = 0, as it should be)
+  const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  k[P][P] -= t * apq;
+  k[Q][Q] += t * apq;
+  k[P][Q] = k[Q][P] = 0.0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (r == P || r == Q) continue;
+    const double rp = k[r][P], rq = k[r][Q];
+    k[r][P] = k[P][r] = c * rp - s * rq;
+    k[r][Q] = k[Q][r] = s * rp + c * rq;
+  }
+}
+
+// The largest eigenvalue of the key matrix of A (the a11..a44 of qcp_solve at
+// lambda = 0).  Sweeps stop when the off-diagonal part is below 2^-60 of the
+// matrix' norm (which rotations keep), 16 at the most.
+// Out of line (`inline` is for the linker): the few lanes that come here must
+// not cost the contraction kernels, which inline their epilogue, registers.
+// A's entries come by value: a pointer to the caller's registers would put
+// them in scratch.
+__host__ __device__ inline __attribute__((noinline)) double qcp_key_lambda_max(double Sxx, double Sxy, double Sxz,
+                                                                               double Syx, double Syy, double Syz,
+                                                                               double Szx, double Szy, double Szz) {
+  double k[4][4];
+  k[0][0] = Sxx + Syy + Szz, k[1][1] = Sxx - Syy - Szz, k[2][2] = Syy - Sxx - Szz, k[3][3] = Szz - Sxx - Syy;
+  k[0][1] = k[1][0] = Syz - Szy, k[0][2] = k[2][0] = Szx - Sxz, k[0][3] = k[3][0] = Sxy - Syx;
+  k[1][2] = k[2][1] = Sxy + Syx, k[1][3] = k[3][1] = Sxz + Szx, k[2][3] = k[3][2] = Syz + Szy;
+  double norm = 0.0;
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) norm += fabs(k[p][q]);
+  if (norm != norm) return norm;  // a non-finite frame stays one
+  for (int sweep = 0; sweep < 16; ++sweep) {
+    const double off = fabs(k[0][1]) + fabs(k[0][2]) + fabs(k[0][3]) + fabs(k[1][2]) + fabs(k[1][3]) + fabs(k[2][3]);
+    if (!(off > 8.673617379884035e-19 * norm)) break;  // 2^-60
+    jacobi_rotate<0, 1>(k), jacobi_rotate<0, 2>(k), jacobi_rotate<0, 3>(k);
+    jacobi_rotate<1, 2>(k), jacobi_rotate<1, 3>(k), jacobi_rotate<2, 3>(k);
+  }
+  const double m01 = k[0][0] > k[1][1] ? k[0][0] : k[1][1];
+  const double m23 = k[2][2] > k[3][3] ? k[2][2] : k[3][3];
+  return m01 > m23 ? m01 : m23;
+}
+
+// A pair's lambda; *path receives the way it was found (RMSF_PAIR_* of
+// rmsf_hip.h).
+__host__ __device__ inline double pair_lambda(const double *A, double E0, int *path) {
+  // two all-zero frames: the quartic is 0 / 0; their distance is 0 (and a
+  // non-finite frame's NaN stays one)
+  if (!(E0 > 0.0)) {
+    *path = RMSF_PAIR_ZERO;
+    return E0;
+  }
+  bool met;
+  double slope;
+  const double l = qcp_newton(A, E0, &met, &slope);
+  // (never true of a NaN: 0 / 0 at an exactly double root met on the first
+  // step -- a frame of collinear atoms against itself)
+  if (met && fabs(slope) >= kPairSlope * fabs(l * l * l)) {
+    *path = RMSF_PAIR_NEWTON;
+    return l;
+  }
+  *path = RMSF_PAIR_JACOBI;
+  return qcp_key_lambda_max(A[0], A[1], A[2], A[3], A[4], A[5], A[6], A[7], A[8]);
 }
 
 // The rotation and the RMSD from that root; the sums and differences of A's

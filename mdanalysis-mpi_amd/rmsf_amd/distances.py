@@ -300,7 +300,10 @@ class CrossDistanceMatrix:
     distance -- the lowest such column where several are equal, which happens:
     the cutoff writes exact zeros and references can be duplicated -- and
     ``results.nearest_dist`` (f64 [F_a]) that distance; both are found on the
-    device before the matrix is copied back (``rmsf_row_argmin``).  With no
+    device before the matrix is copied back (``rmsf_row_argmin``).  A frame
+    with a non-finite coordinate makes its row or column NaN and, as for
+    ``numpy.argmin``, a NaN counts as the least: every row then names the
+    first such reference and its ``nearest_dist`` is NaN.  With no
     frames on either side the matrix is empty, ``nearest`` is -1 and
     ``nearest_dist`` NaN.
 

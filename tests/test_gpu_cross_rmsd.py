@@ -444,7 +444,11 @@ def test_row_argmin(n_cols, pad):
     """Ties planted at known columns -- within one thread's columns (c and c +
     256), across threads, across the halves of the tree; the padding holds
     smaller values than any entry.  numpy.argmin's answer exactly, the values
-    in their bits."""
+    in their bits.  Rows with NaN: numpy.argmin takes a NaN for the least, so
+    the first NaN's column and that NaN come back -- at column 0, at the last
+    column, at 255, 256 and 300, at two columns of different threads (either
+    order of thread and column), in one thread's columns, and beside exact
+    zeros on either side."""
     import torch
 
     from rmsf_amd.engine import Engine
@@ -457,6 +461,21 @@ def test_row_argmin(n_cols, pad):
     for row, cols in enumerate(ties):
         m[row, cols] = 0.0 if row % 2 else 0.5          # exact zeros, as the cutoff writes them, and plain ties
     m[len(ties)] = np.inf                               # nothing below +inf: column 0
+    nans = [t for t in ([0], [n_cols - 1], [255], [256], [300], [3, 200], [200, 3 + 256], [5, 5 + 256], [254, 255, 256],
+                        [127, 128], [999, 1], list(range(n_cols)))
+            if max(t) < n_cols]
+    zeros = [[], [0], [n_cols - 1], [2, 129, 257]]      # exact zeros beside the NaN: before it, after it, none
+    nan_rows = rng.uniform(1.0, 2.0, size=(len(nans) * len(zeros), n_cols))
+    first_nan = []
+    for k, cols in enumerate(nans):
+        for z, zc in enumerate(zeros):
+            row = nan_rows[k * len(zeros) + z]
+            row[[c for c in zc if c < n_cols]] = 0.0
+            row[cols] = np.nan
+            first_nan.append(min(cols))
+    m = np.concatenate([m, nan_rows, np.full((1, n_cols), np.inf)])
+    m[-1, n_cols // 2] = np.nan                         # a NaN among +inf
+    first_nan.append(n_cols // 2)
     buf = torch.full((len(m), n_cols + pad), -1.0, dtype=torch.float64, device="cuda:0")
     buf[:, :n_cols] = torch.tensor(m, device="cuda:0")
     idx, val = eng.row_argmin(buf[:, :n_cols])
@@ -466,6 +485,8 @@ def test_row_argmin(n_cols, pad):
     want = np.argmin(m, axis=1)
     np.testing.assert_array_equal(idx, want)
     np.testing.assert_array_equal(idx[:len(ties)], [t[0] for t in ties])
+    np.testing.assert_array_equal(idx[-len(first_nan):], first_nan)
+    assert np.isnan(val[-len(first_nan):]).all() and not np.isnan(val[:-len(first_nan)]).any()
     assert same_bits(val, m[np.arange(len(m)), want])
 
 
