@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RMSF_ABI_VERSION 3
+#define RMSF_ABI_VERSION 4
 
 #define RMSF_OK 0
 #define RMSF_EINVAL (-1)   /* bad argument (shape, null pointer, size)      */
@@ -759,6 +759,55 @@ int rmsf_row_argmin(const double *d_m, int64_t n_rows, int64_t n_cols,
  * in h_path[k].                                                             */
 int rmsf_pair_lambda_host(const double *h_A, const double *h_E0, int64_t n,
                           double *h_lambda, int32_t *h_path);
+
+/* ---- GROMOS clustering of a symmetric distance matrix (Daura et al. 1999) ---
+ * The definition, the same for the device entries and rmsf_cluster_gromos_host:
+ *   adj(i, j) = (d[i, j] <= cutoff) for i != j, and adj(i, i) = 1 whatever the
+ *   diagonal holds.  A NaN is never a neighbour (a frame with a non-finite
+ *   coordinate has a NaN row and column and ends as a cluster of its own).
+ *   count[i] = the number of set bits of row i.  While any frame is active:
+ *   the centre is the active frame with the largest count -- among equal
+ *   counts the lowest index --, its members adj(centre, .) & active get the
+ *   next cluster id (0, 1, ...) and become inactive, and every frame still
+ *   active loses |adj(i, .) & members| from its count.  Every step removes at
+ *   least its centre, so there are at most n clusters, their sizes do not
+ *   increase, and a cluster's size is its centre's count when it was picked.
+ *   Integers only after the threshold: the same result on every run.
+ * rmsf_adjacency_words(n): the 64-bit words of a row of n bits, (n + 63) / 64
+ *   (0 for n <= 0).
+ * rmsf_adjacency_pack: d_m[n][ld] f64 (ld >= n; columns >= n are not read, the
+ *   matrix is read once) -> d_adj[n][ldw] (ldw >= rmsf_adjacency_words(n)):
+ *   bit j & 63 of word j / 64 of row i is adj(i, j); the bits j >= n of the
+ *   last word are 0 and the words past it are not touched.  d_count[n] (int32)
+ *   receives the rows' counts.  cutoff >= 0 (a NaN is refused).
+ * rmsf_cluster_gromos: the loop on d_adj (symmetric, as the pack of a
+ *   symmetric matrix is) and d_count (read, not changed: the working copy
+ *   lives in d_work, rmsf_cluster_gromos_workspace_bytes(n) bytes, a function
+ *   of n alone).  d_label[n]: the cluster of each frame; d_centre / d_size
+ *   [n], of which the first *h_n_clusters are written: each cluster's centre
+ *   and size (all int32, device).  Two launches a cluster (pick and assign;
+ *   decrement, which walks the members' rows: n^2 / 8 bytes over the whole
+ *   run), enqueued 32 clusters at a time; once the largest count is 1 the
+ *   remaining frames are labelled as singletons in index order by one launch.
+ *   After each batch the call reads one state word back -- its only host
+ *   synchronisation -- and it returns after the last such read: the stream is
+ *   idle and *h_n_clusters (host) is set when it does.
+ * rmsf_cluster_gromos_host: the same definition in plain C++ on a host matrix
+ *   h_m[n][ld]; touches no device; all outputs are host pointers.
+ * n must be in 1..INT32_MAX.                                                 */
+int64_t rmsf_adjacency_words(int64_t n);
+int rmsf_adjacency_pack(const double *d_m, int64_t n, int64_t ld, double cutoff,
+                        uint64_t *d_adj, int64_t ldw, int32_t *d_count,
+                        void *stream);
+size_t rmsf_cluster_gromos_workspace_bytes(int64_t n);
+int rmsf_cluster_gromos(const uint64_t *d_adj, int64_t n, int64_t ldw,
+                        const int32_t *d_count, int32_t *d_label,
+                        int32_t *d_centre, int32_t *d_size,
+                        int32_t *h_n_clusters, void *d_work, size_t work_bytes,
+                        void *stream);
+int rmsf_cluster_gromos_host(const double *h_m, int64_t n, int64_t ld,
+                             double cutoff, int32_t *h_label, int32_t *h_centre,
+                             int32_t *h_size, int32_t *h_n_clusters);
 
 /* ---- qcprot.CalcRMSDRotationalMatrix (RMSF.py:48) --------------------------
  * Batched QCP on device: A[n][9], E0[n], atom counts N[n] -> rot[n][9],

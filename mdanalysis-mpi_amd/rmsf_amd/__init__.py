@@ -19,6 +19,9 @@ Public surface (mirrors the reference's names):
     every frame of another (or to a set of references) and each frame's nearest reference;
     ``hausdorff`` / ``discrete_frechet`` -- the path distances of such a matrix, named as
     MDAnalysis.analysis.psa names them
+  * ``Cluster`` -- GROMOS clustering (Daura et al. 1999) of the frames from their RMSD matrix,
+    which is thresholded into neighbour bits and clustered in HBM without crossing to the host:
+    ``Cluster(traj, cutoff=1.5).run().results.labels`` / ``.centres`` / ``.sizes``
 """
 from ._lib import RmsfEmptyError, RmsfError, load as load_library
 from .parallel import blocks
@@ -28,6 +31,7 @@ from .rms import RMSF, Results
 from .eigen import PCAConvergenceError
 from .pca import PCA, cosine_content, cumulative_overlap, pca_from_comoment, rmsip
 from .distances import CrossDistanceMatrix, DiffusionMap, DistanceMatrix, discrete_frechet, hausdorff
+from .clustering import Cluster
 
 __all__ = [
     "RMSF",
@@ -43,6 +47,7 @@ __all__ = [
     "CrossDistanceMatrix",
     "hausdorff",
     "discrete_frechet",
+    "Cluster",
     "blocks",
     "second_order_moments",
     "get_rotation_matrix",

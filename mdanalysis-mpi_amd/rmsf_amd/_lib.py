@@ -23,7 +23,7 @@ RMSF_MODE_SUM = 1
 RMSF_XFORM_DOUBLES = 16
 RMSF_MAX_SPLIT_FRAMES = 4096  # frames per accumulate split (Welford coefficient table)
 RMSF_REFINFO_DOUBLES = 2064  # 16-double record + reduction scratch
-ABI_VERSION = 3
+ABI_VERSION = 4
 RMSF_PAIR_NEWTON = 0  # how rmsf_pair_lambda_host found a pair's lambda
 RMSF_PAIR_JACOBI = 1
 RMSF_PAIR_ZERO = 2
@@ -126,6 +126,11 @@ SIGNATURES = {
                                 c_int, c_double, P, c_int64, P, c_size_t, P]),
     "rmsf_row_argmin": (c_int, [P, c_int64, c_int64, c_int64, P, P, P]),
     "rmsf_pair_lambda_host": (c_int, [P, P, c_int64, P, P]),
+    "rmsf_adjacency_words": (c_int64, [c_int64]),
+    "rmsf_adjacency_pack": (c_int, [P, c_int64, c_int64, c_double, P, c_int64, P, P]),
+    "rmsf_cluster_gromos_workspace_bytes": (c_size_t, [c_int64]),
+    "rmsf_cluster_gromos": (c_int, [P, c_int64, c_int64, P, P, P, P, P, P, c_size_t, P]),
+    "rmsf_cluster_gromos_host": (c_int, [P, c_int64, c_int64, c_double, P, P, P, P]),
     "rmsf_qcp_batch": (c_int, [P, P, P, c_int64, P, P, P]),
     "rmsf_calc_rmsd_rotational_matrix": (c_int, [P, P, c_int64, P, P, POINTER(c_double)]),
     "rmsf_synth_frames": (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_uint64, P, P]),

@@ -40,13 +40,16 @@ _PW_PLANES = ('DistanceMatrix reads (frame, atom, xyz) rows; HBM-resident coordi
 MAX_GATHER = 65535  # frames one rmsf_gather_frames launch takes
 
 
-def check_pairwise_memory(eng: Engine, n_frames: int, dense_bytes: int = 0) -> None:
+def check_pairwise_memory(eng: Engine, n_frames: int, dense_bytes: int = 0, bits: bool = False) -> None:
     """MemoryError if the [F, F] f64 result plus the dense copy of the
-    selected rows (when one is made) is over half the free HBM."""
+    selected rows (when one is made) is over half the free HBM.  ``bits``
+    (``Cluster``): plus the F^2 / 8 bytes of the neighbour bits."""
     need = 8 * n_frames * n_frames
     free = torch.cuda.mem_get_info(eng.device)[0]
-    if need + dense_bytes > free // 2:
+    bit_bytes = 8 * n_frames * ((n_frames + 63) // 64) if bits else 0
+    if need + dense_bytes + bit_bytes > free // 2:
         raise MemoryError(f"DistanceMatrix: the [{n_frames}, {n_frames}] f64 matrix needs {need} bytes"
+                          + (f", its neighbour bits {bit_bytes} bytes" if bit_bytes else "")
                           + (f" and the dense copy of the selected rows {dense_bytes} bytes" if dense_bytes else "")
                           + f", over half of the {free} bytes of free HBM")
 
@@ -213,40 +216,48 @@ class DistanceMatrix:
             raise NotImplementedError("DistanceMatrix runs on one device per process: not under torch.distributed "
                                       "with more than one rank")
 
-    # -- the frames, dense in HBM -------------------------------------------
-    def _resident(self, eng: Engine, src, fl: FrameList):
+    def _matrix_hbm(self, eng: Engine, start=None, stop=None, step=None, frames=None, bits: bool = False):
+        """The device part of ``run``: ``results.frames`` / ``n_frames`` are
+        set and (the [F, F] f64 matrix as an HBM tensor, what its kernels read)
+        is returned, the kernels enqueued on the current stream and not waited
+        for: the caller holds the second until it has synchronised.  (None,
+        None) with no frames.  ``bits``: the memory check also counts a bit
+        matrix (``Cluster``).  Call it under ``torch.cuda.device(eng.device)``."""
+        src, masses = make_source(self._input, select=self.select, align=None, batch_frames=self.batch_frames,
+                                  layout=self.layout, group_masses=isinstance(self.weights, str))
+        n_sel = src.n_sel
+        _check_n_sel(n_sel)
+        w = _check_weights(masses if isinstance(self.weights, str) else self.weights, n_sel)
+        fl = FrameList(src.n_traj, start, stop, step, frames=frames)
         n_frames = len(fl)
-        return resident_frames(eng, src, fl, self.batch_frames,
-                               lambda dense_bytes: check_pairwise_memory(eng, n_frames, dense_bytes))
+        r = self.results
+        r.frames = _frame_rows(fl)
+        r.n_frames = self.n_frames = n_frames
+        if n_frames == 0:
+            return None, None
+        keep, ptr, fstride, sel = resident_frames(
+            eng, src, fl, self.batch_frames,
+            lambda dense_bytes: check_pairwise_memory(eng, n_frames, dense_bytes, bits=bits))
+        w_dev = None if w is None else torch.tensor(w, device=eng.device)
+        w_total = float(n_sel) if w is None else float(w.sum())
+        centre, g = eng.pairwise_centres(ptr, fstride, n_frames, n_sel, sel, w_dev, self.superposition)
+        need = eng.pairwise_workspace_bytes(n_frames, n_sel)
+        work = eng.empty(need // 8) if need else None
+        out = eng.empty(n_frames, n_frames)
+        eng.pairwise_rmsd(ptr, fstride, n_frames, n_sel, sel, w_dev, w_total, centre, g, out,
+                          superpose=self.superposition, cutoff=self.cutoff, work=work)
+        return out, (src, keep, w_dev, centre, g, work)
 
     def run(self, start=None, stop=None, step=None, frames=None, **kwargs):
         self._refuse()
         eng = Engine(self.device)
         with torch.cuda.device(eng.device):
-            src, masses = make_source(self._input, select=self.select, align=None, batch_frames=self.batch_frames,
-                                      layout=self.layout, group_masses=isinstance(self.weights, str))
-            n_sel = src.n_sel
-            _check_n_sel(n_sel)
-            w = _check_weights(masses if isinstance(self.weights, str) else self.weights, n_sel)
-            fl = FrameList(src.n_traj, start, stop, step, frames=frames)
-            n_frames = len(fl)
-            r = self.results
-            r.frames = _frame_rows(fl)
-            r.n_frames = self.n_frames = n_frames
-            if n_frames == 0:
-                r.dist_matrix = np.zeros((0, 0))
+            out, keep = self._matrix_hbm(eng, start, stop, step, frames)
+            if out is None:
+                self.results.dist_matrix = np.zeros((0, 0))
                 return self
-            keep, ptr, fstride, sel = self._resident(eng, src, fl)
-            w_dev = None if w is None else torch.tensor(w, device=eng.device)
-            w_total = float(n_sel) if w is None else float(w.sum())
-            centre, g = eng.pairwise_centres(ptr, fstride, n_frames, n_sel, sel, w_dev, self.superposition)
-            need = eng.pairwise_workspace_bytes(n_frames, n_sel)
-            work = eng.empty(need // 8) if need else None
-            out = eng.empty(n_frames, n_frames)
-            eng.pairwise_rmsd(ptr, fstride, n_frames, n_sel, sel, w_dev, w_total, centre, g, out,
-                              superpose=self.superposition, cutoff=self.cutoff, work=work)
             torch.cuda.current_stream(eng.device).synchronize()
-            r.dist_matrix = out.cpu().numpy()
+            self.results.dist_matrix = out.cpu().numpy()
             del keep
         return self
 

@@ -590,6 +590,42 @@ class Engine:
              self.stream)
         return idx, val
 
+    # -- GROMOS clustering of a distance matrix (csrc/clustering.hip) ------------
+    def adjacency_words(self, n: int) -> int:
+        return int(self.lib.rmsf_adjacency_words(n))
+
+    def adjacency_pack(self, m: torch.Tensor, cutoff: float, n: int | None = None, ldw: int | None = None):
+        """(uint64 words as int64 [n, ldw], int32 [n]): the neighbour bits
+        ``adj(i, j) = (m[i, j] <= cutoff)``, diagonal set, NaN never a
+        neighbour, bit j & 63 of word j // 64, and their row counts
+        (rmsf_adjacency_pack).  ``m``: f64 [>= n, >= n] in HBM, read once."""
+        n = m.shape[0] if n is None else n
+        if m.dtype != F64 or m.dim() != 2 or m.stride(1) != 1 or m.shape[0] < n or m.shape[1] < n or n < 1:
+            raise ValueError("adjacency_pack: buffer sizes")
+        ldw = self.adjacency_words(n) if ldw is None else ldw
+        adj = torch.empty((n, ldw), dtype=torch.int64, device=self.device)
+        count = torch.empty(n, dtype=torch.int32, device=self.device)
+        call("rmsf_adjacency_pack", m.data_ptr(), n, m.stride(0), float(cutoff), adj.data_ptr(), adj.stride(0),
+             count.data_ptr(), self.stream)
+        return adj, count
+
+    def cluster_gromos(self, adj: torch.Tensor, count: torch.Tensor):
+        """(labels int32 [n], centres int32 [k], sizes int32 [k]) in HBM: the
+        GROMOS loop on adjacency_pack's bits and counts (rmsf_cluster_gromos;
+        ``count`` is left as it is).  Returns after the loop's last read of
+        its state: the stream is idle."""
+        n = adj.shape[0]
+        if (adj.dtype != torch.int64 or adj.dim() != 2 or adj.stride(1) != 1 or count.dtype != torch.int32
+                or count.numel() < n or not count.is_contiguous() or adj.shape[1] < self.adjacency_words(n) or n < 1):
+            raise ValueError("cluster_gromos: buffer sizes")
+        label, centre, size = (torch.empty(n, dtype=torch.int32, device=self.device) for _ in range(3))
+        need = int(self.lib.rmsf_cluster_gromos_workspace_bytes(n))
+        work = torch.empty(need // 8, dtype=torch.int64, device=self.device)
+        k = ctypes.c_int32(0)
+        call("rmsf_cluster_gromos", adj.data_ptr(), n, adj.stride(0), count.data_ptr(), label.data_ptr(),
+             centre.data_ptr(), size.data_ptr(), ctypes.byref(k), work.data_ptr(), need, self.stream)
+        return label, centre[:k.value], size[:k.value]
+
     def qcp_batch(self, A: torch.Tensor, E0: torch.Tensor, N: torch.Tensor):
         n = A.shape[0]
         rot = self.empty(n, 9)

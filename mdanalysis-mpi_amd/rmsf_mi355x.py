@@ -57,6 +57,12 @@ def main(argv=None) -> int:
     ap.add_argument("--dist-matrix", default=None, metavar="OUT.npy",
                     help="also write the all-pairs RMSD matrix of the selected atoms' frames, f64 [F, F] "
                          "(rmsf_amd.DistanceMatrix; each pair superposed unless --align none; one process only)")
+    ap.add_argument("--cluster", default=None, metavar="OUT.npy",
+                    help="also write the GROMOS cluster of every frame, int64 [F], clusters numbered from the largest "
+                         "(rmsf_amd.Cluster on the RMSD matrix --dist-matrix writes, which stays in HBM; needs "
+                         "--cluster-cutoff; one process only)")
+    ap.add_argument("--cluster-cutoff", type=float, default=None, metavar="C",
+                    help="--cluster: the cluster radius in A, frames within C of each other are neighbours")
     ap.add_argument("--cross-rmsd", default=None, metavar="OUT.npy",
                     help="also write the RMSD of every frame of the trajectory to every frame of --cross-with, "
                          "f64 [F, F_b] (rmsf_amd.CrossDistanceMatrix; each pair superposed unless --align none; "
@@ -84,6 +90,12 @@ def main(argv=None) -> int:
         ap.error(f"--pca-solver {a.pca_solver} needs --n-components")
     if a.dist_matrix and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--dist-matrix runs in one process (no torch.distributed launch)")
+    if bool(a.cluster) != (a.cluster_cutoff is not None):
+        ap.error("--cluster OUT.npy and --cluster-cutoff C go together")
+    if a.cluster and not a.cluster_cutoff >= 0.0:
+        ap.error("--cluster-cutoff must be >= 0")
+    if a.cluster and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--cluster runs in one process (no torch.distributed launch)")
     if bool(a.cross_rmsd) != bool(a.cross_with):
         ap.error("--cross-rmsd OUT.npy and --cross-with TRAJ go together")
     if a.cross_rmsd and a.synthetic:
@@ -175,6 +187,12 @@ def main(argv=None) -> int:
         dm = DistanceMatrix(dm_input, superposition=align is not None, **dm_kw).run().results
         print(f"RMSD matrix over {dm.n_frames} frames: max {dm.dist_matrix.max():.6f} A", flush=True)
         np.save(a.dist_matrix, dm.dist_matrix)
+    if a.cluster:
+        from rmsf_amd import Cluster
+        cl = Cluster(dm_input, cutoff=a.cluster_cutoff, superposition=align is not None, **dm_kw).run().results
+        print(f"GROMOS clusters at {a.cluster_cutoff} A over {cl.n_frames} frames: {cl.n_clusters}, the largest of "
+              f"{int(cl.sizes[0]) if cl.n_clusters else 0} frames", flush=True)
+        np.save(a.cluster, cl.labels)
     if a.cross_rmsd:
         from rmsf_amd import CrossDistanceMatrix
         cm = CrossDistanceMatrix(dm_input, cross_b, superposition=align is not None, **dm_kw).run().results
