@@ -794,6 +794,22 @@ int rmsf_pair_lambda_host(const double *h_A, const double *h_E0, int64_t n,
  *   idle and *h_n_clusters (host) is set when it does.
  * rmsf_cluster_gromos_host: the same definition in plain C++ on a host matrix
  *   h_m[n][ld]; touches no device; all outputs are host pointers.
+ * rmsf_adjacency_count: d_count[i] = the set bits of the rmsf_adjacency_words(n)
+ *   words of row i of d_adj[n][ldw] (words past them are not read): one
+ *   wavefront a row, a fixed order, no atomics, the bits read once.
+ * rmsf_pairwise_adjacency: the bits rmsf_pairwise_rmsd (cutoff = zero_cutoff)
+ *   followed by rmsf_adjacency_pack (cutoff) would give, word for word,
+ *   without the n_frames^2 f64 matrix between them: the inputs, the plan, the
+ *   workspace (rmsf_pairwise_workspace_bytes) and the distance of every pair
+ *   are rmsf_pairwise_rmsd's, and each 16 x 16 tile of pairs stores, in place
+ *   of its distances, the 16-bit segments of its rows (and of its mirror's) --
+ *   plain 2-byte stores to different quarters of the 64-bit words, no atomics.
+ *   Rows >= n_frames and words past rmsf_adjacency_words(n_frames) are not
+ *   touched, the bits j >= n_frames of the last word are 0.  d_count may be
+ *   NULL; otherwise rmsf_adjacency_count runs after.  cutoff >= 0 (a NaN is
+ *   refused), ldw >= rmsf_adjacency_words(n_frames); more than INT32_MAX tile
+ *   pairs (n_frames above about 1,048,000) are refused, as everything else is,
+ *   before any launch.
  * n must be in 1..INT32_MAX.                                                 */
 int64_t rmsf_adjacency_words(int64_t n);
 int rmsf_adjacency_pack(const double *d_m, int64_t n, int64_t ld, double cutoff,
@@ -808,6 +824,16 @@ int rmsf_cluster_gromos(const uint64_t *d_adj, int64_t n, int64_t ldw,
 int rmsf_cluster_gromos_host(const double *h_m, int64_t n, int64_t ld,
                              double cutoff, int32_t *h_label, int32_t *h_centre,
                              int32_t *h_size, int32_t *h_n_clusters);
+int rmsf_adjacency_count(const uint64_t *d_adj, int64_t n, int64_t ldw,
+                         int32_t *d_count, void *stream);
+int rmsf_pairwise_adjacency(const float *d_xyz, int64_t frame_stride,
+                            int64_t n_frames, int64_t n_sel,
+                            const int32_t *d_sel, const double *d_weights,
+                            double w_total, const double *d_centre,
+                            const double *d_g, int superpose,
+                            double zero_cutoff, double cutoff, uint64_t *d_adj,
+                            int64_t ldw, int32_t *d_count, void *d_work,
+                            size_t work_bytes, void *stream);
 
 /* ---- qcprot.CalcRMSDRotationalMatrix (RMSF.py:48) --------------------------
  * Batched QCP on device: A[n][9], E0[n], atom counts N[n] -> rot[n][9],

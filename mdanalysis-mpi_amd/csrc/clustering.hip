@@ -8,6 +8,7 @@
 //   leave, and every frame still active loses its neighbours among them.
 //
 // k_adj_pack        f64 matrix -> bit rows (one ballot a word) and the counts.
+// k_adj_count       the counts of bit rows written elsewhere (csrc/pairwise.hip).
 // k_gromos_init     the working copy of the counts, the active words, the state.
 // k_gromos_pick     one workgroup: argmax, member words, labels, member list.
 // k_gromos_decrement  one workgroup a column word: walks the members' rows.
@@ -35,6 +36,7 @@ constexpr int kWave = 64;
 #endif
 constexpr int kPackWaves = RMSF_PACK_WAVES;
 constexpr int kPackUnroll = RMSF_PACK_UNROLL;
+constexpr int kCountWaves = 4;    // rows a workgroup of k_adj_count
 constexpr int kPickBlock = 1024;  // the one workgroup of k_gromos_pick
 constexpr int kPickWaves = kPickBlock / kWave;
 constexpr int kDecWaves = 8;      // waves sharing one column word's member list
@@ -105,6 +107,25 @@ __global__ __launch_bounds__(kPackWaves *kWave) void k_adj_pack(const double *__
     for (int k = 0; k < kPackWaves; ++k) sum += s_cnt[k];
     count[row] = sum;
   }
+}
+
+// ---- count ---------------------------------------------------------------------
+// The counts of bit rows that were not packed here (rmsf_pairwise_adjacency
+// writes them a tile at a time, each row from many workgroups).  One wave a
+// row: lane l adds the popcounts of words l, l + 64, ... in order, the lanes
+// are added by a halving tree of shuffles.  The bits are read once.
+__global__ __launch_bounds__(kCountWaves *kWave) void k_adj_count(const uint64_t *__restrict__ adj, int64_t n,
+                                                                  int64_t ldw, int32_t *__restrict__ count) {
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int64_t row = (int64_t)blockIdx.x * kCountWaves + wave;
+  if (row >= n) return;  // (a whole wave; nothing below is shared between waves)
+  const int64_t n_words = adj_words(n);
+  const uint64_t *__restrict__ a = adj + row * ldw;
+  int cnt = 0;
+#pragma unroll 4
+  for (int64_t w = lane; w < n_words; w += kWave) cnt += __popcll(a[w]);
+  for (int d = kWave / 2; d > 0; d >>= 1) cnt += __shfl_down(cnt, d);
+  if (lane == 0) count[row] = cnt;
 }
 
 // ---- the loop ------------------------------------------------------------------
@@ -269,6 +290,14 @@ RMSF_EXPORT int rmsf_adjacency_pack(const double *d_m, int64_t n, int64_t ld, do
   hipLaunchKernelGGL(k_adj_pack, dim3((unsigned)n), dim3(kPackWaves * kWave), 0, S(stream), d_m, n, ld, cutoff, d_adj,
                      ldw, d_count);
   return after_launch("k_adj_pack");
+}
+
+RMSF_EXPORT int rmsf_adjacency_count(const uint64_t *d_adj, int64_t n, int64_t ldw, int32_t *d_count, void *stream) {
+  if (!d_adj || !d_count || n < 1 || n > INT32_MAX || ldw < adj_words(n))
+    return fail(RMSF_EINVAL, "rmsf_adjacency_count: bad arguments");
+  hipLaunchKernelGGL(k_adj_count, dim3((unsigned)((n + kCountWaves - 1) / kCountWaves)), dim3(kCountWaves * kWave), 0,
+                     S(stream), d_adj, n, ldw, d_count);
+  return after_launch("k_adj_count");
 }
 
 RMSF_EXPORT size_t rmsf_cluster_gromos_workspace_bytes(int64_t n) {

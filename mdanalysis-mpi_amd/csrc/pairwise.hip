@@ -27,7 +27,10 @@
 //   * pair_epilogue lambda by Newton's iteration, by Jacobi on the key matrix
 //                   where the largest root is not simple (or the trace,
 //                   without superposition), the cutoff, the store and its
-//                   mirror.
+//                   mirror -- of the distances, or (rmsf_pairwise_adjacency)
+//                   of the bits d <= radius alone, as 16-bit segments of the
+//                   rows of csrc/clustering.hip's neighbour bits, so that the
+//                   f64 matrix is never stored.
 //
 // The rectangle d[i, j] = RMSD(A_i, B_j) of two trajectories is the same
 // contraction with a second operand of its own (base, stride, selection,
@@ -44,6 +47,8 @@
 
 #include <cmath>
 #include <cstdint>
+#include <string>
+#include <type_traits>
 
 #include "dense_f64.h"
 #include "rmsf_device.h"
@@ -61,6 +66,10 @@ constexpr int kPasses = kKA / kAtomLanes;  // atoms a lane stages
 constexpr int kPairs = kTF * kTF;          // frame pairs of a tile pair: one per thread
 constexpr int kTile = 9 * kPairs;          // A_ij entries of a tile pair
 constexpr int64_t kTargetGroups = 512;     // 2 resident workgroups per CU on MI355X
+// Tile pairs a launch of k_pw_tiles: a grid's threads along x (workgroups x kBlock) must stay below 2^32 -- a
+// launch of more is not refused, it runs the count modulo 2^32 (seen at 200,000 frames, 78 M tile pairs: 14 % of
+// them ran) -- so more pairs than this go in several launches.
+constexpr int64_t kMaxGroups = int64_t(1) << 23;
 
 static_assert(kPairs == kBlock, "the epilogue gives every thread one frame pair");
 static_assert(kTile <= 2 * kKA * kPitch, "the waves' sum reuses the staging buffer");
@@ -164,21 +173,78 @@ __device__ __forceinline__ double pair_distance(const double *A, double gi, doub
   return d <= cutoff ? 0.0 : d;
 }
 
+// What a tile pair stores: its distances as f64, or (BITS) only whether each is
+// within a radius -- rows of the neighbour bits of csrc/clustering.hip, which
+// are addressed here in the 16-bit quarters of their 64-bit words: tile column
+// J of a row is element J of uint16 [n][4 ldw].
+template <bool BITS>
+using PairOut = std::conditional_t<BITS, uint16_t, double>;
+
+// The 16 predicates of tile row (tid >> 4), one a lane, as that row's segment
+// of the bit matrix: a wave is 4 tile rows x 16 columns, so its ballot is four
+// such segments, and the row's first lane stores its own with one 2-byte
+// vector store.  Tiles that share a 64-bit word write different quarters of
+// it, so no store meets another.  With `tail` (the last tile column of the
+// row) the quarters of the row's last word that no tile covers are cleared
+// too: elements [n_tiles, quarters).  Called by every lane of every wave.
+__device__ __forceinline__ void store_row_bits(bool bit, bool row_in, uint16_t *__restrict__ row, int64_t q,
+                                               bool tail, int64_t n_tiles, int64_t quarters) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t b = __ballot(bit);
+  if ((lane & 15) == 0 && row_in) {
+    row[q] = (uint16_t)(b >> (lane & 48));
+    if (tail)
+      for (int64_t z = n_tiles; z < quarters; ++z) row[z] = 0;
+  }
+}
+
+// pair_epilogue's BITS form: bit (i, j) = (i == j) || (d <= radius) of the
+// same d (a NaN is never within it), columns >= n_frames 0, rows >= n_frames
+// not written; the mirror's predicate is read from sd as the f64 mirror is.
+__device__ __forceinline__ void pair_epilogue_bits(double d, int64_t I, int64_t J, int64_t n_frames, double radius,
+                                                   uint16_t *__restrict__ out, int64_t ld,
+                                                   double (*__restrict__ sd)[kTF + 1]) {
+  const int tid = threadIdx.x;
+  const int fi = tid >> 4, fj = tid & 15;
+  const int64_t i = kTF * I + fi, j = kTF * J + fj;
+  const bool in = i < n_frames && j < n_frames;
+  const int64_t n_tiles = (n_frames + kTF - 1) / kTF, quarters = 4 * ((n_frames + 63) / 64);
+  const bool tail = J == n_tiles - 1;
+  if (I == J) {
+    if (fj > fi) sd[fi][fj] = d, sd[fj][fi] = d;
+    if (fj == fi) sd[fi][fi] = 0.0;
+    __syncthreads();
+    store_row_bits(in && (fi == fj || sd[fi][fj] <= radius), i < n_frames, out + i * ld, J, tail, n_tiles, quarters);
+  } else {
+    sd[fi][fj] = d;
+    store_row_bits(in && d <= radius, i < n_frames, out + i * ld, J, tail, n_tiles, quarters);
+    __syncthreads();
+    const int64_t jj = kTF * J + fi, ii = kTF * I + fj;  // row of tile J, column of tile I
+    store_row_bits(jj < n_frames && ii < n_frames && sd[fj][fi] <= radius, jj < n_frames, out + jj * ld, I, false,
+                   n_tiles, quarters);
+  }
+}
+
 // Thread tid owns the frame pair (fi = tid >> 4 of tile I, fj = tid & 15 of
 // tile J) and its A_ij.  Pairs j > i are computed; each value goes to [i, j]
 // and, through LDS so that both stores run along rows, to [j, i]; the
-// diagonal is written as 0.  Called by every thread of the workgroup.
+// diagonal is written as 0.  BITS: the same distances, stored as neighbour
+// bits within `radius` (pair_epilogue_bits).  Called by every thread of the
+// workgroup.
+template <bool BITS>
 __device__ __forceinline__ void pair_epilogue(const double *A, int64_t I, int64_t J, int64_t n_frames,
                                               const double *__restrict__ g, int superpose, double w_total,
-                                              double cutoff, double *__restrict__ out, int64_t ld,
-                                              double (*__restrict__ sd)[kTF + 1]) {
+                                              double cutoff, double radius, PairOut<BITS> *__restrict__ out,
+                                              int64_t ld, double (*__restrict__ sd)[kTF + 1]) {
   const int tid = threadIdx.x;
   const int fi = tid >> 4, fj = tid & 15;
   const int64_t i = kTF * I + fi, j = kTF * J + fj;
   const bool in = i < n_frames && j < n_frames;
   double d = 0.0;
   if (in && j > i) d = pair_distance(A, g[i], g[j], superpose, w_total, cutoff);
-  if (I == J) {
+  if constexpr (BITS) {
+    pair_epilogue_bits(d, I, J, n_frames, radius, out, ld, sd);
+  } else if (I == J) {
     // the tile is its own mirror image: the upper half fills both
     if (fj > fi) sd[fi][fj] = d, sd[fj][fi] = d;
     if (fj == fi) sd[fi][fi] = 0.0;
@@ -193,30 +259,31 @@ __device__ __forceinline__ void pair_epilogue(const double *A, int64_t I, int64_
   }
 }
 
-// One workgroup: tile pair blockIdx.x, atoms [blockIdx.y ks_atoms, ...).
+// One workgroup: tile pair pair0 + blockIdx.x, atoms [blockIdx.y ks_atoms, ...).
 // Staging: lane (tid & 15) walks the atoms of frame (tid >> 4) of the tile;
 // its three deviations f64(x) - c_f go to sm[op][atom k][16 c + frame]
 // (operand A times the atom's weight), so an MFMA operand (mfma_3x3,
 // dense_f64.h) is 16 consecutive doubles of staged atom k, and
 // acc[ci][cj][reg] of lane l is entry (ci, cj) of A_ij for frames
 // i = (l >> 4) + 4 reg of tile I and j = l & 15 of tile J.
-template <bool GATHER, bool WEIGHTED>
+template <bool GATHER, bool WEIGHTED, bool BITS>
 __global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict__ xyz, int64_t fstride,
                                                      int64_t n_frames, int64_t n_sel,
                                                      const int32_t *__restrict__ sel,
                                                      const double *__restrict__ weights,
                                                      const double *__restrict__ centre,
                                                      const double *__restrict__ g, int superpose, double w_total,
-                                                     double cutoff, double *__restrict__ out, int64_t ld,
+                                                     double cutoff, double radius,
+                                                     PairOut<BITS> *__restrict__ out, int64_t ld,
                                                      double *__restrict__ work, int64_t n_tiles, int64_t n_pairs,
-                                                     int64_t ks_atoms, int direct) {
+                                                     int64_t ks_atoms, int direct, int64_t pair0) {
   __shared__ double sm[2 * kKA * kPitch];  // A then B deviations; reused for the waves' sum
   __shared__ double sd[kTF][kTF + 1];      // the tile's distances, for the mirrored store
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int ta = tid & (kAtomLanes - 1), tf = tid >> 4;
-  const int64_t pair = blockIdx.x, ks = blockIdx.y;
+  const int64_t pair = pair0 + blockIdx.x, ks = blockIdx.y;
   int64_t I, J;
   pair_to_tiles(pair, n_tiles, I, J);
   // a weighted diagonal tile still needs both operands: w d and d
@@ -311,7 +378,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict_
     double A[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) A[q] = sm[kPairs * q + tid];
-    pair_epilogue(A, I, J, n_frames, g, superpose, w_total, cutoff, out, ld, sd);
+    pair_epilogue<BITS>(A, I, J, n_frames, g, superpose, w_total, cutoff, radius, out, ld, sd);
   } else {
     double *__restrict__ w = work + ((int64_t)ks * n_pairs + pair) * kTile;
     for (int e = tid; e < kTile; e += kBlock) w[e] = sm[e];
@@ -320,10 +387,12 @@ __global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict_
 
 // The n_ks partials of every A_ij entry, summed in atom-range order, then
 // the epilogue.  One workgroup per tile pair.
+template <bool BITS>
 __global__ __launch_bounds__(kBlock) void k_pw_fold(const double *__restrict__ work, int64_t n_frames,
                                                     int64_t n_tiles, int64_t n_pairs, int64_t n_ks,
                                                     const double *__restrict__ g, int superpose, double w_total,
-                                                    double cutoff, double *__restrict__ out, int64_t ld) {
+                                                    double cutoff, double radius, PairOut<BITS> *__restrict__ out,
+                                                    int64_t ld) {
   __shared__ double sd[kTF][kTF + 1];
   const int tid = threadIdx.x;
   const int64_t pair = blockIdx.x;
@@ -337,7 +406,7 @@ __global__ __launch_bounds__(kBlock) void k_pw_fold(const double *__restrict__ w
     for (int64_t k = 0; k < n_ks; ++k) s += w[k * n_pairs * kTile];
     A[q] = s;
   }
-  pair_epilogue(A, I, J, n_frames, g, superpose, w_total, cutoff, out, ld, sd);
+  pair_epilogue<BITS>(A, I, J, n_frames, g, superpose, w_total, cutoff, radius, out, ld, sd);
 }
 
 // ---- the rectangle: every frame of A against every frame of B ---------------
@@ -589,6 +658,49 @@ int launch_centres(const char *who, const float *d_xyz, int64_t fstride, int64_t
   return after_launch("k_pw_centres");
 }
 
+// k_pw_tiles and, with more than one atom range, k_pw_fold over every tile
+// pair of n_frames frames, storing distances (out f64 [n][ld]) or, BITS, the
+// neighbour bits within `radius` (out uint16 [n][ld], ld in 16-bit elements).
+// Everything that can be refused is refused before the first launch; the
+// pointers and sizes that do not depend on the plan are the caller's, already
+// checked, and `who` names it in the messages.
+template <bool BITS>
+int launch_pairs(const char *who, const float *d_xyz, int64_t fstride, int64_t n_frames, int64_t n_sel,
+                 const int32_t *d_sel, const double *d_weights, double w_total, const double *d_centre,
+                 const double *d_g, int superpose, double cutoff, double radius, PairOut<BITS> *d_out, int64_t ld,
+                 void *d_work, size_t work_bytes, void *stream) {
+  if (n_frames == 0) return RMSF_OK;
+  const PwPlan pl = pw_plan(n_frames, n_sel);
+  if (pl.n_pairs > INT32_MAX || pl.n_ks > 65535)
+    return fail(RMSF_EINVAL, std::string(who) + ": too many frames for one launch");
+  const size_t need = pw_work_doubles(pl) * sizeof(double);
+  if (need && (!d_work || work_bytes < need)) return fail(RMSF_ENOMEM, std::string(who) + ": workspace too small");
+  const int direct = pl.n_ks == 1;
+  double *work = static_cast<double *>(d_work);
+  const dim3 block(kBlock);
+#define PW_LAUNCH(G_, W_)                                                                                      \
+  hipLaunchKernelGGL((k_pw_tiles<G_, W_, BITS>), grid, block, 0, S(stream), d_xyz, fstride, n_frames, n_sel,   \
+                     d_sel, d_weights, d_centre, d_g, superpose, w_total, cutoff, radius, d_out, ld, work,     \
+                     pl.n_tiles, pl.n_pairs, pl.ks_atoms, direct, p0)
+  const bool gt = d_sel != nullptr, wt = d_weights != nullptr;
+  // kMaxGroups tile pairs a launch (past 352 frames there is one atom range, and below there is one launch)
+  for (int64_t p0 = 0; p0 < pl.n_pairs; p0 += kMaxGroups) {
+    const dim3 grid((unsigned)std::min<int64_t>(kMaxGroups, pl.n_pairs - p0), (unsigned)pl.n_ks);
+    if (gt && wt) PW_LAUNCH(true, true);
+    else if (gt) PW_LAUNCH(true, false);
+    else if (wt) PW_LAUNCH(false, true);
+    else PW_LAUNCH(false, false);
+    if (int rc = after_launch("k_pw_tiles")) return rc;
+  }
+#undef PW_LAUNCH
+  if (!direct) {
+    hipLaunchKernelGGL(k_pw_fold<BITS>, dim3((unsigned)pl.n_pairs), block, 0, S(stream), work, n_frames, pl.n_tiles,
+                       pl.n_pairs, pl.n_ks, d_g, superpose, w_total, cutoff, radius, d_out, ld);
+    if (int rc = after_launch("k_pw_fold")) return rc;
+  }
+  return RMSF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -623,32 +735,25 @@ RMSF_EXPORT int rmsf_pairwise_rmsd(const float *d_xyz, int64_t fstride, int64_t 
   if (!d_xyz || !d_centre || !d_g || !d_out || n_sel < 1 || n_frames < 0 || fstride < 0 || ld < n_frames ||
       !(w_total > 0.0))
     return fail(RMSF_EINVAL, "rmsf_pairwise_rmsd: bad arguments");
-  if (n_frames == 0) return RMSF_OK;
-  const PwPlan pl = pw_plan(n_frames, n_sel);
-  if (pl.n_pairs > INT32_MAX || pl.n_ks > 65535)
-    return fail(RMSF_EINVAL, "rmsf_pairwise_rmsd: too many frames for one launch");
-  const size_t need = pw_work_doubles(pl) * sizeof(double);
-  if (need && (!d_work || work_bytes < need)) return fail(RMSF_ENOMEM, "rmsf_pairwise_rmsd: workspace too small");
-  const int direct = pl.n_ks == 1;
-  double *work = static_cast<double *>(d_work);
-  const dim3 grid((unsigned)pl.n_pairs, (unsigned)pl.n_ks), block(kBlock);
-#define PW_LAUNCH(G_, W_)                                                                                     \
-  hipLaunchKernelGGL((k_pw_tiles<G_, W_>), grid, block, 0, S(stream), d_xyz, fstride, n_frames, n_sel, d_sel, \
-                     d_weights, d_centre, d_g, superpose, w_total, cutoff, d_out, ld, work, pl.n_tiles,       \
-                     pl.n_pairs, pl.ks_atoms, direct)
-  const bool gt = d_sel != nullptr, wt = d_weights != nullptr;
-  if (gt && wt) PW_LAUNCH(true, true);
-  else if (gt) PW_LAUNCH(true, false);
-  else if (wt) PW_LAUNCH(false, true);
-  else PW_LAUNCH(false, false);
-#undef PW_LAUNCH
-  if (int rc = after_launch("k_pw_tiles")) return rc;
-  if (!direct) {
-    hipLaunchKernelGGL(k_pw_fold, dim3((unsigned)pl.n_pairs), block, 0, S(stream), work, n_frames, pl.n_tiles,
-                       pl.n_pairs, pl.n_ks, d_g, superpose, w_total, cutoff, d_out, ld);
-    if (int rc = after_launch("k_pw_fold")) return rc;
-  }
-  return RMSF_OK;
+  return launch_pairs<false>("rmsf_pairwise_rmsd", d_xyz, fstride, n_frames, n_sel, d_sel, d_weights, w_total,
+                             d_centre, d_g, superpose, cutoff, 0.0, d_out, ld, d_work, work_bytes, stream);
+}
+
+RMSF_EXPORT int rmsf_pairwise_adjacency(const float *d_xyz, int64_t fstride, int64_t n_frames, int64_t n_sel,
+                                        const int32_t *d_sel, const double *d_weights, double w_total,
+                                        const double *d_centre, const double *d_g, int superpose,
+                                        double zero_cutoff, double cutoff, uint64_t *d_adj, int64_t ldw,
+                                        int32_t *d_count, void *d_work, size_t work_bytes, void *stream) {
+  if (!d_xyz || !d_centre || !d_g || !d_adj || n_sel < 1 || n_frames < 0 || fstride < 0 ||
+      ldw < rmsf_adjacency_words(n_frames) || !(w_total > 0.0) || !(cutoff >= 0.0))
+    return fail(RMSF_EINVAL, "rmsf_pairwise_adjacency: bad arguments");
+  // a row as its 16-bit quarters: tile column J is element J of uint16 [n_frames][4 ldw]
+  if (int rc = launch_pairs<true>("rmsf_pairwise_adjacency", d_xyz, fstride, n_frames, n_sel, d_sel, d_weights,
+                                  w_total, d_centre, d_g, superpose, zero_cutoff, cutoff,
+                                  reinterpret_cast<uint16_t *>(d_adj), 4 * ldw, d_work, work_bytes, stream))
+    return rc;
+  if (!d_count || n_frames == 0) return RMSF_OK;
+  return rmsf_adjacency_count(d_adj, n_frames, ldw, d_count, stream);
 }
 
 RMSF_EXPORT size_t rmsf_cross_workspace_bytes(int64_t n_a, int64_t n_b, int64_t n_sel) {

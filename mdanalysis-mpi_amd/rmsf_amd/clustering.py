@@ -7,7 +7,9 @@ with the most neighbours and its neighbours form the first cluster and leave,
 and so on until no frame is left.  After the one threshold it is all integers
 (csrc/clustering.hip): the F x F f64 matrix is packed into F^2 / 8 bytes of
 neighbour bits where it lies in HBM and never crosses to the host, and the
-result is the same on every run.
+result is the same on every run.  Where that matrix does not fit
+(``matrix="bits"``, and "auto" then) the pair kernel writes the bits itself
+and the matrix is never stored (csrc/pairwise.hip, ``pair_epilogue``).
 
 The definition, shared with ``rmsf_cluster_gromos_host`` (include/rmsf_hip.h):
 ``adj(i, j) = (d[i, j] <= cutoff)``, the diagonal always set, a NaN never a
@@ -52,6 +54,16 @@ class Cluster:
     keep_matrix : bool
         True: ``results.dist_matrix`` is the host copy of the f64 matrix.
         False (the default): the matrix is not copied to the host.
+    matrix : "auto" | "f64" | "bits"
+        How a trajectory's neighbour bits are made.  "f64": the F x F f64
+        matrix is stored in HBM (8 F^2 bytes), packed and freed.  "bits": the
+        pair kernel's epilogue writes the bits themselves
+        (``rmsf_pairwise_adjacency``) -- the same words, F^2 / 8 bytes and no
+        matrix, which is what fits at 10^5 - 10^6 frames; not with
+        ``keep_matrix=True`` or a matrix as the input (ValueError).  "auto"
+        (the default): "f64" wherever that fits in half the free HBM, or a
+        matrix is asked for or given; "bits" where it does not; MemoryError
+        only if the bits do not fit either.
 
     ``run(start, stop, step)`` or ``run(frames=...)`` as ``DistanceMatrix.run``
     (trajectory and ``DistanceMatrix`` inputs).  Results:
@@ -61,6 +73,9 @@ class Cluster:
     ``results.centres``  int64 [n_clusters]: the row of each cluster's centre;
                          ``results.frames[centres]`` are trajectory frames.
     ``results.sizes``    int64 [n_clusters], non-increasing.
+    ``results.n_neighbours``  int64 [F]: the frames within ``cutoff`` of each
+                         row, itself included (the bit rows' counts).
+    ``results.matrix_form``  "f64" or "bits", whichever ran.
     ``results.n_clusters``, ``results.frames``, ``results.n_frames``.
 
     A supplied matrix must be square and its neighbour relation ``d <=
@@ -72,9 +87,11 @@ class Cluster:
 
     def __init__(self, x, *, cutoff: float, method: str = "gromos", select=None, weights=None,
                  superposition: bool = True, zero_cutoff: float = 1e-5, layout: str = "fac", device=None,
-                 batch_frames: int | None = None, keep_matrix: bool = False, gpus=None):
+                 batch_frames: int | None = None, keep_matrix: bool = False, matrix: str = "auto", gpus=None):
         if method != "gromos":
             raise ValueError(f"method must be 'gromos', got {method!r}")
+        if matrix not in ("auto", "f64", "bits"):
+            raise ValueError(f"matrix must be 'auto', 'f64' or 'bits', got {matrix!r}")
         cutoff = float(cutoff)
         if not cutoff >= 0.0:
             raise ValueError(f"cutoff must be >= 0, got {cutoff}")
@@ -90,6 +107,13 @@ class Cluster:
         self.gpus = gpus
         self.layout = layout
         self._dm = None
+        given = isinstance(x, DistanceMatrix) or self._is_matrix(x)
+        if matrix == "bits" and (keep_matrix or given):
+            raise ValueError('matrix="bits" stores no f64 matrix: not with '
+                             + ("keep_matrix=True" if keep_matrix else "a distance matrix as the input")
+                             + ' (use matrix="f64" or "auto")')
+        # a matrix that is asked for, or given, is a stored one
+        self.matrix = "f64" if matrix == "auto" and (keep_matrix or given) else matrix
         if isinstance(x, DistanceMatrix):
             self._dm = x
         elif not self._is_matrix(x):
@@ -128,6 +152,8 @@ class Cluster:
         r.labels = np.zeros(0, dtype=np.int64)
         r.centres = np.zeros(0, dtype=np.int64)
         r.sizes = np.zeros(0, dtype=np.int64)
+        r.n_neighbours = np.zeros(0, dtype=np.int64)
+        r.matrix_form = None  # nothing ran
         r.n_clusters = 0
         r.n_frames = self.n_frames = 0
         r.frames = np.zeros(0, dtype=np.int64) if n_frames_rows is None else n_frames_rows
@@ -139,6 +165,8 @@ class Cluster:
         x, dm, r = self._input, self._dm, self.results
         host = None  # a host copy of the matrix that exists anyway
         keep = None  # what the matrix kernels read, held until the loop has synchronised
+        d = adj = count = None
+        form = "f64"
         if dm is x and dm.results.get("dist_matrix") is None:
             dm.run(start, stop, step, frames=frames)
         eng = Engine(self.device if dm is not x else dm.device)
@@ -147,9 +175,12 @@ class Cluster:
                 host = dm.results.dist_matrix
                 rows = dm.results.frames
                 d = torch.as_tensor(host, device=eng.device) if host.size else None
-            elif dm is not None:
+            elif dm is not None and self.matrix == "f64":
                 d, keep = dm._matrix_hbm(eng, start, stop, step, frames, bits=True)
                 rows = dm.results.frames
+            elif dm is not None:
+                adj, count, keep = dm._adjacency_hbm(eng, self.cutoff, start, stop, step, frames, matrix=self.matrix)
+                rows, form = dm.results.frames, dm.matrix_form
             else:
                 if isinstance(x, np.ndarray):
                     host = np.ascontiguousarray(x, dtype=np.float64)
@@ -163,20 +194,23 @@ class Cluster:
                     if d is not None and not bool(torch.equal(d <= self.cutoff, (d <= self.cutoff).T)):
                         raise ValueError(_ASYMMETRIC)
                 rows = np.arange(x.shape[0], dtype=np.int64)
-            if d is None:
+            if d is None and adj is None:
                 return self._empty(rows)
-            n = d.shape[0]
-            adj, count = eng.adjacency_pack(d, self.cutoff)
-            if self.keep_matrix and host is None:
-                host = d.cpu().numpy()
-            del d  # the f64 matrix is not needed past the pack
+            if adj is None:
+                adj, count = eng.adjacency_pack(d, self.cutoff)
+                if self.keep_matrix and host is None:
+                    host = d.cpu().numpy()
+                del d  # the f64 matrix is not needed past the pack
+            n = adj.shape[0]
             label, centre, size = eng.cluster_gromos(adj, count)
             del keep
             r.labels = label.cpu().numpy().astype(np.int64)
             r.centres = centre.cpu().numpy().astype(np.int64)
             r.sizes = size.cpu().numpy().astype(np.int64)
+            r.n_neighbours = count.cpu().numpy().astype(np.int64)
             r.n_clusters = int(r.centres.size)
             r.frames = np.asarray(rows, dtype=np.int64)
             r.n_frames = self.n_frames = n
+            r.matrix_form = form
             r.dist_matrix = host if self.keep_matrix else None
         return self

@@ -40,13 +40,25 @@ _PW_PLANES = ('DistanceMatrix reads (frame, atom, xyz) rows; HBM-resident coordi
 MAX_GATHER = 65535  # frames one rmsf_gather_frames launch takes
 
 
-def check_pairwise_memory(eng: Engine, n_frames: int, dense_bytes: int = 0, bits: bool = False) -> None:
+def check_pairwise_memory(eng: Engine, n_frames: int, dense_bytes: int = 0, bits: bool = False,
+                          matrix: bool = True) -> None:
     """MemoryError if the [F, F] f64 result plus the dense copy of the
     selected rows (when one is made) is over half the free HBM.  ``bits``
-    (``Cluster``): plus the F^2 / 8 bytes of the neighbour bits."""
-    need = 8 * n_frames * n_frames
+    (``Cluster``): plus the F^2 / 8 bytes of the neighbour bits.  ``matrix``
+    False, the bits-only form (``Cluster(matrix="bits")``, where no f64 matrix
+    is stored): the neighbour bits and the dense copy alone.  The split-K
+    workspace is in neither form: it exists only up to 352 frames (256 tile
+    pairs) and is at most 512 tile pairs' partials, 9.4 MB whatever the
+    atoms -- the other half of the free HBM is there for such."""
     free = torch.cuda.mem_get_info(eng.device)[0]
-    bit_bytes = 8 * n_frames * ((n_frames + 63) // 64) if bits else 0
+    bit_bytes = 8 * n_frames * ((n_frames + 63) // 64) if bits or not matrix else 0
+    if not matrix:
+        if bit_bytes + dense_bytes > free // 2:
+            raise MemoryError(f"Cluster: the neighbour bits of {n_frames} frames need {bit_bytes} bytes"
+                              + (f" and the dense copy of the selected rows {dense_bytes} bytes" if dense_bytes else "")
+                              + f", over half of the {free} bytes of free HBM")
+        return
+    need = 8 * n_frames * n_frames
     if need + dense_bytes + bit_bytes > free // 2:
         raise MemoryError(f"DistanceMatrix: the [{n_frames}, {n_frames}] f64 matrix needs {need} bytes"
                           + (f", its neighbour bits {bit_bytes} bytes" if bit_bytes else "")
@@ -189,6 +201,7 @@ class DistanceMatrix:
         self.gpus = gpus
         self.results = Results()
         self.n_frames = None
+        self.matrix_form = None  # set by _adjacency_hbm
 
     # -- what can be refused without a device ------------------------------
     def _n_sel_hint(self):
@@ -216,13 +229,13 @@ class DistanceMatrix:
             raise NotImplementedError("DistanceMatrix runs on one device per process: not under torch.distributed "
                                       "with more than one rank")
 
-    def _matrix_hbm(self, eng: Engine, start=None, stop=None, step=None, frames=None, bits: bool = False):
-        """The device part of ``run``: ``results.frames`` / ``n_frames`` are
-        set and (the [F, F] f64 matrix as an HBM tensor, what its kernels read)
-        is returned, the kernels enqueued on the current stream and not waited
-        for: the caller holds the second until it has synchronised.  (None,
-        None) with no frames.  ``bits``: the memory check also counts a bit
-        matrix (``Cluster``).  Call it under ``torch.cuda.device(eng.device)``."""
+    def _pairs_hbm(self, eng: Engine, start, stop, step, frames, check):
+        """What the matrix and the neighbour bits share: the source, the frame
+        list (``results.frames`` / ``n_frames`` are set), the frames' residency,
+        their centres and the split-K workspace.  ``check(n_frames,
+        dense_bytes)`` runs before anything is allocated.  Returns
+        (the arguments of ``Engine.pairwise_rmsd`` up to ``g``, work, what
+        the kernels read), or None with no frames."""
         src, masses = make_source(self._input, select=self.select, align=None, batch_frames=self.batch_frames,
                                   layout=self.layout, group_masses=isinstance(self.weights, str))
         n_sel = src.n_sel
@@ -234,19 +247,74 @@ class DistanceMatrix:
         r.frames = _frame_rows(fl)
         r.n_frames = self.n_frames = n_frames
         if n_frames == 0:
-            return None, None
-        keep, ptr, fstride, sel = resident_frames(
-            eng, src, fl, self.batch_frames,
-            lambda dense_bytes: check_pairwise_memory(eng, n_frames, dense_bytes, bits=bits))
+            return None
+        keep, ptr, fstride, sel = resident_frames(eng, src, fl, self.batch_frames,
+                                                  lambda dense_bytes: check(n_frames, dense_bytes))
         w_dev = None if w is None else torch.tensor(w, device=eng.device)
         w_total = float(n_sel) if w is None else float(w.sum())
         centre, g = eng.pairwise_centres(ptr, fstride, n_frames, n_sel, sel, w_dev, self.superposition)
         need = eng.pairwise_workspace_bytes(n_frames, n_sel)
         work = eng.empty(need // 8) if need else None
+        return (ptr, fstride, n_frames, n_sel, sel, w_dev, w_total, centre, g), work, (src, keep, w_dev, centre, g, work)
+
+    def _matrix_hbm(self, eng: Engine, start=None, stop=None, step=None, frames=None, bits: bool = False):
+        """The device part of ``run``: ``results.frames`` / ``n_frames`` are
+        set and (the [F, F] f64 matrix as an HBM tensor, what its kernels read)
+        is returned, the kernels enqueued on the current stream and not waited
+        for: the caller holds the second until it has synchronised.  (None,
+        None) with no frames.  ``bits``: the memory check also counts a bit
+        matrix (``Cluster``).  Call it under ``torch.cuda.device(eng.device)``."""
+        pairs = self._pairs_hbm(eng, start, stop, step, frames,
+                                lambda n, dense: check_pairwise_memory(eng, n, dense, bits=bits))
+        if pairs is None:
+            return None, None
+        args, work, keep = pairs
+        return self._store_matrix(eng, args, work), keep
+
+    def _store_matrix(self, eng: Engine, args, work) -> torch.Tensor:
+        n_frames = args[2]
         out = eng.empty(n_frames, n_frames)
-        eng.pairwise_rmsd(ptr, fstride, n_frames, n_sel, sel, w_dev, w_total, centre, g, out,
-                          superpose=self.superposition, cutoff=self.cutoff, work=work)
-        return out, (src, keep, w_dev, centre, g, work)
+        eng.pairwise_rmsd(*args, out, superpose=self.superposition, cutoff=self.cutoff, work=work)
+        return out
+
+    def _adjacency_hbm(self, eng: Engine, cutoff: float, start=None, stop=None, step=None, frames=None,
+                       matrix: str = "bits"):
+        """``_matrix_hbm`` for the neighbour bits within ``cutoff`` alone:
+        (uint64 words as int64 [F, words], int32 [F] row counts, what the
+        kernels read), enqueued and not waited for; (None, None, None) with no
+        frames.  ``matrix`` "bits": the pair kernel's epilogue writes the bits
+        and no f64 matrix is stored (``Engine.pairwise_adjacency``); the memory
+        check is ``check_pairwise_memory``'s bits-only form.  "auto": where
+        the stored matrix passes that check as it stands, the matrix is
+        stored, packed and freed, as ``_matrix_hbm`` and
+        ``Engine.adjacency_pack`` do; the bits alone otherwise.
+        ``self.matrix_form`` is "f64" or "bits", whichever ran."""
+        form = [matrix]
+
+        def check(n, dense):
+            if form[0] == "auto":
+                try:
+                    check_pairwise_memory(eng, n, dense, bits=True)
+                    form[0] = "f64"
+                    return
+                except MemoryError:
+                    form[0] = "bits"
+            check_pairwise_memory(eng, n, dense, matrix=False)
+
+        pairs = self._pairs_hbm(eng, start, stop, step, frames, check)
+        if pairs is None:
+            return None, None, None
+        args, work, keep = pairs
+        self.matrix_form = form[0]
+        if form[0] == "f64":
+            adj, count = eng.adjacency_pack(self._store_matrix(eng, args, work), cutoff)
+            return adj, count, keep
+        n_frames = args[2]
+        adj = torch.empty((n_frames, eng.adjacency_words(n_frames)), dtype=torch.int64, device=eng.device)
+        count = torch.empty(n_frames, dtype=torch.int32, device=eng.device)
+        eng.pairwise_adjacency(*args, adj, count, cutoff, superpose=self.superposition, zero_cutoff=self.cutoff,
+                               work=work)
+        return adj, count, keep
 
     def run(self, start=None, stop=None, step=None, frames=None, **kwargs):
         self._refuse()

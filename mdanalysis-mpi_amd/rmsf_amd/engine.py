@@ -609,6 +609,40 @@ class Engine:
              count.data_ptr(), self.stream)
         return adj, count
 
+    def _is_adjacency(self, adj: torch.Tensor, n: int) -> bool:
+        return (adj.dtype == torch.int64 and adj.dim() == 2 and adj.stride(1) == 1 and adj.shape[0] >= n >= 1
+                and adj.shape[1] >= self.adjacency_words(n))
+
+    def pairwise_adjacency(self, xyz_ptr: int, fstride: int, n_frames: int, n_sel: int, sel, weights,
+                           w_total: float, centre: torch.Tensor, g: torch.Tensor, adj: torch.Tensor,
+                           count: torch.Tensor | None, cutoff: float, superpose: bool = True,
+                           zero_cutoff: float = 0.0, work: torch.Tensor | None = None) -> None:
+        """adj[:n_frames] (uint64 words as int64 [>= n_frames, ldw]) = the
+        neighbour bits that pairwise_rmsd(cutoff=zero_cutoff) followed by
+        adjacency_pack(cutoff) would give, word for word, and ``count`` (int32
+        [>= n_frames], or None) their row counts, without the f64 matrix
+        (rmsf_pairwise_adjacency).  ``centre``, ``g``, ``work``: as
+        pairwise_rmsd's."""
+        if (centre.dtype != F64 or g.dtype != F64 or centre.numel() < 3 * n_frames or g.numel() < n_frames
+                or not centre.is_contiguous() or not self._is_adjacency(adj, n_frames)
+                or (count is not None and (count.dtype != torch.int32 or count.numel() < n_frames
+                                           or not count.is_contiguous()))):
+            raise ValueError("pairwise_adjacency: buffer sizes")
+        call("rmsf_pairwise_adjacency", xyz_ptr, fstride, n_frames, n_sel, _ptr(sel), _ptr(weights), float(w_total),
+             centre.data_ptr(), g.data_ptr(), int(bool(superpose)), float(zero_cutoff), float(cutoff),
+             adj.data_ptr(), adj.stride(0), _ptr(count),
+             _ptr(work), 0 if work is None else work.numel() * work.element_size(), self.stream)
+
+    def adjacency_count(self, adj: torch.Tensor, n: int | None = None) -> torch.Tensor:
+        """int32 [n]: the set bits of every row of ``adj[:n]``'s
+        adjacency_words(n) words (rmsf_adjacency_count)."""
+        n = adj.shape[0] if n is None else n
+        if not self._is_adjacency(adj, n):
+            raise ValueError("adjacency_count: buffer sizes")
+        count = torch.empty(n, dtype=torch.int32, device=self.device)
+        call("rmsf_adjacency_count", adj.data_ptr(), n, adj.stride(0), count.data_ptr(), self.stream)
+        return count
+
     def cluster_gromos(self, adj: torch.Tensor, count: torch.Tensor):
         """(labels int32 [n], centres int32 [k], sizes int32 [k]) in HBM: the
         GROMOS loop on adjacency_pack's bits and counts (rmsf_cluster_gromos;

@@ -63,6 +63,11 @@ def main(argv=None) -> int:
                          "--cluster-cutoff; one process only)")
     ap.add_argument("--cluster-cutoff", type=float, default=None, metavar="C",
                     help="--cluster: the cluster radius in A, frames within C of each other are neighbours")
+    ap.add_argument("--cluster-matrix", choices=["auto", "f64", "bits"], default=None,
+                    help="--cluster: 'f64' stores the F x F RMSD matrix in HBM and packs it into neighbour bits; "
+                         "'bits' has the pair kernel write the bits and stores no matrix (F^2 / 8 bytes: what fits "
+                         "at 10^5 - 10^6 frames); 'auto' (the default) takes 'f64' where it fits and 'bits' where "
+                         "it does not")
     ap.add_argument("--cross-rmsd", default=None, metavar="OUT.npy",
                     help="also write the RMSD of every frame of the trajectory to every frame of --cross-with, "
                          "f64 [F, F_b] (rmsf_amd.CrossDistanceMatrix; each pair superposed unless --align none; "
@@ -92,6 +97,8 @@ def main(argv=None) -> int:
         ap.error("--dist-matrix runs in one process (no torch.distributed launch)")
     if bool(a.cluster) != (a.cluster_cutoff is not None):
         ap.error("--cluster OUT.npy and --cluster-cutoff C go together")
+    if a.cluster_matrix and not a.cluster:
+        ap.error(f"--cluster-matrix {a.cluster_matrix} needs --cluster")
     if a.cluster and not a.cluster_cutoff >= 0.0:
         ap.error("--cluster-cutoff must be >= 0")
     if a.cluster and int(os.environ.get("WORLD_SIZE", 1)) > 1:
@@ -189,9 +196,12 @@ def main(argv=None) -> int:
         np.save(a.dist_matrix, dm.dist_matrix)
     if a.cluster:
         from rmsf_amd import Cluster
-        cl = Cluster(dm_input, cutoff=a.cluster_cutoff, superposition=align is not None, **dm_kw).run().results
+        cl = Cluster(dm_input, cutoff=a.cluster_cutoff, superposition=align is not None,
+                     matrix=a.cluster_matrix or "auto", **dm_kw).run().results
         print(f"GROMOS clusters at {a.cluster_cutoff} A over {cl.n_frames} frames: {cl.n_clusters}, the largest of "
-              f"{int(cl.sizes[0]) if cl.n_clusters else 0} frames", flush=True)
+              f"{int(cl.sizes[0]) if cl.n_clusters else 0} frames (neighbour bits from "
+              f"{'the stored f64 matrix' if cl.matrix_form == 'f64' else 'the pair kernel, no matrix stored'})",
+              flush=True)
         np.save(a.cluster, cl.labels)
     if a.cross_rmsd:
         from rmsf_amd import CrossDistanceMatrix
