@@ -15,14 +15,13 @@
 // the minimal RMSD without the rotation (Theobald 2005).
 //
 //   * k_pw_centres  one workgroup per frame: the weighted centre and G_f.
-//   * k_pw_tiles    one workgroup per (macro tile pair J >= I, atom range):
-//                   16 frames = 48 coordinates a side, rows coordinate-major
-//                   (row = 16 c + frame), 3 x 3 tiles of
-//                   v_mfma_f64_16x16x4_f64 per wave.  The deviations of 32
-//                   atoms are staged as f64 [atom][row] in LDS; each of the
-//                   4 waves contracts 8 of them.  With that row order one
-//                   lane's nine accumulators hold the nine entries of A_ij of
-//                   one frame pair per register.
+//   * k_pw_tiles    one workgroup per (macro tile pair, atom range): 16 frames
+//                   = 48 coordinates a side, rows coordinate-major (row = 16 c
+//                   + frame), 3 x 3 tiles of v_mfma_f64_16x16x4_f64 per wave.
+//                   The deviations of 32 atoms are staged as f64 [atom][row]
+//                   in LDS; each of the 4 waves contracts 8 of them.  With
+//                   that row order one lane's nine accumulators hold the nine
+//                   entries of A_ij of one frame pair per register.
 //   * k_pw_fold     the split-K partials, summed in atom-range order.
 //   * pair_epilogue lambda by Newton's iteration, by Jacobi on the key matrix
 //                   where the largest root is not simple (or the trace,
@@ -33,16 +32,21 @@
 //                   f64 matrix is never stored.
 //
 // The rectangle d[i, j] = RMSD(A_i, B_j) of two trajectories is the same
-// contraction with a second operand of its own (base, stride, selection,
-// centres, G):
+// contraction with a second operand side of its own (Side: base, stride,
+// selection, centres, G), so both shapes are one kernel template, one fold,
+// one plan (TilePlan) and one launcher (launch_tiles); the square fills both
+// sides from the same arrays.  What stays with the shape (RECT):
 //
-//   * k_pw_cross_tiles  one workgroup per (tile I of A, tile J of B, atom
-//                       range), the whole tile rectangle; operand 0 is the A
-//                       tile and carries the weight.
-//   * k_pw_cross_fold   its split-K partials, summed in atom-range order.
-//   * cross_epilogue    pair_epilogue without the mirror: one store a pair.
-//   * k_row_argmin      one workgroup per row: the first least entry, a NaN
-//                       below every number.
+//   * tiles_of_pair   the tile pairs J >= I of the square's upper triangle, or
+//                     the whole tile rectangle, pair = I tiles_b + J;
+//   * n_ops           an unweighted diagonal tile of the square stages one
+//                     operand; the rectangle always both (operand 0 is the A
+//                     tile and carries the weight);
+//   * tile_epilogue   pair_epilogue, or cross_epilogue: the same distance
+//                     without the mirror, one store a pair.
+//
+//   * k_row_argmin    one workgroup per row: the first least entry, a NaN
+//                     below every number.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -75,26 +79,50 @@ static_assert(kPairs == kBlock, "the epilogue gives every thread one frame pair"
 static_assert(kTile <= 2 * kKA * kPitch, "the waves' sum reuses the staging buffer");
 static_assert(sizeof(double) * (2 * kKA * kPitch + kTF * (kTF + 1)) <= kLdsLimit, "sm and sd fit");
 
-// The work decomposition, a function of (n_frames, n_sel) alone, so the
-// workspace layout and the summation order are fixed by the sizes.
-struct PwPlan {
-  int64_t n_tiles;   // macro tiles a side
-  int64_t n_pairs;   // tile pairs J >= I
-  int64_t n_ks;      // atom ranges (split-K); 1 = the epilogue runs in k_pw_tiles
-  int64_t ks_atoms;  // atoms per range, a multiple of kKA
+// One operand side of a tile pair: n frames at xyz + f fstride, their
+// selection (NULL: atoms 0..n_sel-1), centres and G.  The square matrix has
+// the same side twice.
+struct Side {
+  const float *xyz;
+  int64_t fstride;
+  int64_t n;
+  const int32_t *sel;
+  const double *centre;
+  const double *g;
 };
 
-PwPlan pw_plan(int64_t n_frames, int64_t n_sel) {
-  PwPlan p;
-  p.n_tiles = (n_frames + kTF - 1) / kTF;
-  p.n_pairs = p.n_tiles * (p.n_tiles + 1) / 2;
-  const SplitK k = split_k(std::max<int64_t>(1, (n_sel + kKA - 1) / kKA), p.n_pairs, kTargetGroups, 1);
+// The work decomposition, a function of the frame counts and n_sel alone, so
+// the workspace layout and the summation order are fixed by the sizes.
+struct TilePlan {
+  int64_t tiles_a, tiles_b;  // macro tiles a side (the square: the same twice)
+  int64_t n_pairs;           // tile pairs: J >= I of the square, pair = I tiles_b + J of the rectangle;
+                             // 0 = a rectangle of more than a launch sequence takes
+  int64_t n_ks;              // atom ranges (split-K); 1 = the epilogue runs in k_pw_tiles
+  int64_t ks_atoms;          // atoms per range, a multiple of kKA
+};
+
+TilePlan tile_plan(int64_t tiles_a, int64_t tiles_b, int64_t n_pairs, int64_t n_sel) {
+  TilePlan p{tiles_a, tiles_b, n_pairs, 0, 0};
+  if (n_pairs == 0) return p;
+  const SplitK k = split_k(std::max<int64_t>(1, (n_sel + kKA - 1) / kKA), n_pairs, kTargetGroups, 1);
   p.n_ks = k.n_ks;
   p.ks_atoms = k.per * kKA;
   return p;
 }
 
-size_t pw_work_doubles(const PwPlan &p) {
+TilePlan pw_plan(int64_t n_frames, int64_t n_sel) {
+  const int64_t t = (n_frames + kTF - 1) / kTF;
+  return tile_plan(t, t, t * (t + 1) / 2, n_sel);
+}
+
+TilePlan cross_plan(int64_t n_a, int64_t n_b, int64_t n_sel) {
+  const int64_t ta = (n_a + kTF - 1) / kTF, tb = (n_b + kTF - 1) / kTF;
+  // (each factor first: the product of two int64 tile counts may not fit)
+  const bool fits = ta <= INT32_MAX && tb <= INT32_MAX && ta * tb <= INT32_MAX;
+  return tile_plan(ta, tb, fits ? ta * tb : 0, n_sel);
+}
+
+size_t work_doubles(const TilePlan &p) {
   if (p.n_ks <= 1) return 0;
   return (size_t)p.n_ks * (size_t)p.n_pairs * kTile;
 }
@@ -259,53 +287,95 @@ __device__ __forceinline__ void pair_epilogue(const double *A, int64_t I, int64_
   }
 }
 
-// One workgroup: tile pair pair0 + blockIdx.x, atoms [blockIdx.y ks_atoms, ...).
+// Thread tid owns the pair (fi = tid >> 4 of A's tile I, fj = tid & 15 of B's
+// tile J) and its A_ij: pair_epilogue's arithmetic, one store, no mirror (fj
+// is the fastest index: the stores of 16 lanes run along a row).
+__device__ __forceinline__ void cross_epilogue(const double *A, int64_t I, int64_t J, int64_t n_a, int64_t n_b,
+                                               const double *__restrict__ g_a, const double *__restrict__ g_b,
+                                               int superpose, double w_total, double cutoff,
+                                               double *__restrict__ out, int64_t ld) {
+  const int tid = threadIdx.x;
+  const int64_t i = kTF * I + (tid >> 4), j = kTF * J + (tid & 15);
+  if (i >= n_a || j >= n_b) return;
+  out[i * ld + j] = pair_distance(A, g_a[i], g_b[j], superpose, w_total, cutoff);
+}
+
+// What differs between the two shapes, for k_pw_tiles and k_pw_fold alike: the
+// tile pair of a pair index, and the epilogue -- the square's with its sd tile
+// (the tile's distances, for the mirrored store) from side a alone.
+template <bool RECT>
+__device__ __forceinline__ void tiles_of_pair(int64_t pair, int64_t tiles_b, int64_t &I, int64_t &J) {
+  if constexpr (RECT) {
+    I = pair / tiles_b, J = pair - I * tiles_b;
+  } else {
+    pair_to_tiles(pair, tiles_b, I, J);
+  }
+}
+
+template <bool RECT, bool BITS>
+__device__ __forceinline__ void tile_epilogue(const double *A, int64_t I, int64_t J, int64_t n_a, int64_t n_b,
+                                              const double *__restrict__ g_a, const double *__restrict__ g_b,
+                                              int superpose, double w_total, double cutoff, double radius,
+                                              PairOut<BITS> *__restrict__ out, int64_t ld) {
+  if constexpr (RECT) {
+    cross_epilogue(A, I, J, n_a, n_b, g_a, g_b, superpose, w_total, cutoff, out, ld);
+  } else {
+    __shared__ double sd[kTF][kTF + 1];
+    pair_epilogue<BITS>(A, I, J, n_a, g_a, superpose, w_total, cutoff, radius, out, ld, sd);
+  }
+}
+
+// One workgroup: tile pair pair0 + blockIdx.x, atoms [blockIdx.y ks_atoms, ...),
+// of the square (tiles J >= I of side sa against itself; sb is not read) or,
+// RECT, of the rectangle (tile I of sa against tile J of sb).
 // Staging: lane (tid & 15) walks the atoms of frame (tid >> 4) of the tile;
 // its three deviations f64(x) - c_f go to sm[op][atom k][16 c + frame]
-// (operand A times the atom's weight), so an MFMA operand (mfma_3x3,
-// dense_f64.h) is 16 consecutive doubles of staged atom k, and
+// (operand 0, the tile of sa, times the atom's weight), so an MFMA operand
+// (mfma_3x3, dense_f64.h) is 16 consecutive doubles of staged atom k, and
 // acc[ci][cj][reg] of lane l is entry (ci, cj) of A_ij for frames
-// i = (l >> 4) + 4 reg of tile I and j = l & 15 of tile J.
-template <bool GATHER, bool WEIGHTED, bool BITS>
-__global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict__ xyz, int64_t fstride,
-                                                     int64_t n_frames, int64_t n_sel,
-                                                     const int32_t *__restrict__ sel,
-                                                     const double *__restrict__ weights,
-                                                     const double *__restrict__ centre,
-                                                     const double *__restrict__ g, int superpose, double w_total,
-                                                     double cutoff, double radius,
+// i = (l >> 4) + 4 reg of tile I and j = l & 15 of tile J.  An unweighted
+// diagonal tile of the square stages one operand and contracts it with itself;
+// a tile of A and a tile of B are different data also where I = J.  GATHER:
+// some side has a selection -- which, is the same for the whole grid.
+template <bool GATHER, bool WEIGHTED, bool RECT, bool BITS>
+__global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(Side sa, Side sb_rect, int64_t n_sel,
+                                                     const double *__restrict__ weights, int superpose,
+                                                     double w_total, double cutoff, double radius,
                                                      PairOut<BITS> *__restrict__ out, int64_t ld,
-                                                     double *__restrict__ work, int64_t n_tiles, int64_t n_pairs,
+                                                     double *__restrict__ work, int64_t tiles_b, int64_t n_pairs,
                                                      int64_t ks_atoms, int direct, int64_t pair0) {
   __shared__ double sm[2 * kKA * kPitch];  // A then B deviations; reused for the waves' sum
-  __shared__ double sd[kTF][kTF + 1];      // the tile's distances, for the mirrored store
 
+  const Side &sb = RECT ? sb_rect : sa;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int ta = tid & (kAtomLanes - 1), tf = tid >> 4;
   const int64_t pair = pair0 + blockIdx.x, ks = blockIdx.y;
   int64_t I, J;
-  pair_to_tiles(pair, n_tiles, I, J);
+  tiles_of_pair<RECT>(pair, tiles_b, I, J);
   // a weighted diagonal tile still needs both operands: w d and d
-  const int n_ops = (I == J && !WEIGHTED) ? 1 : 2;
+  const int n_ops = (!RECT && I == J && !WEIGHTED) ? 1 : 2;
 
   const int64_t a0 = ks * ks_atoms;
   const int64_t a1 = a0 + ks_atoms < n_sel ? a0 + ks_atoms : n_sel;
 
   // The lane's frame of each operand tile: its row, its centre, and whether
-  // it exists.  A lane past the last frame reads the last frame instead (and
-  // an atom past the range's end the range's last atom), so every load is
-  // unconditional and in bounds, and its deviation is zeroed after.
+  // it exists.  A lane past a side's last frame reads that side's last frame
+  // instead (and an atom past the range's end the range's last atom), so every
+  // load is unconditional and in bounds, and its deviation is zeroed after.
   const float *p_op[2];
+  const int32_t *sel_op[2];
   double cen[2][3];
   bool live[2];
 #pragma unroll
   for (int op = 0; op < 2; ++op) {
+    const Side &s = op ? sb : sa;
     const int64_t f = kTF * (op ? J : I) + tf;
-    live[op] = f < n_frames;
-    const int64_t fc = live[op] ? f : n_frames - 1;
-    p_op[op] = xyz + fc * fstride;
-    cen[op][0] = centre[3 * fc], cen[op][1] = centre[3 * fc + 1], cen[op][2] = centre[3 * fc + 2];
+    live[op] = f < s.n;
+    const int64_t fc = live[op] ? f : s.n - 1;
+    p_op[op] = s.xyz + fc * s.fstride;
+    sel_op[op] = s.sel;
+    cen[op][0] = s.centre[3 * fc], cen[op][1] = s.centre[3 * fc + 1], cen[op][2] = s.centre[3 * fc + 2];
   }
 
   f64x4 acc[3][3];
@@ -324,11 +394,12 @@ __global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict_
     for (int pass = 0; pass < kPasses; ++pass) {
       const int64_t a = ab + pass * kAtomLanes + ta;
       const int64_t ac = a < a1 ? a : a1 - 1;
-      const int64_t row = 3 * (GATHER ? (int64_t)sel[ac] : ac);
       if (WEIGHTED) wv[pass] = weights[ac];
 #pragma unroll
       for (int op = 0; op < 2; ++op) {
         if (op >= n_ops) break;
+        // (the square's one selection is there whenever GATHER is)
+        const int64_t row = 3 * (GATHER && (!RECT || sel_op[op]) ? (int64_t)sel_op[op][ac] : ac);
         const float *__restrict__ q = p_op[op] + row;
         raw[op][pass][0] = q[0], raw[op][pass][1] = q[1], raw[op][pass][2] = q[2];
       }
@@ -378,7 +449,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict_
     double A[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) A[q] = sm[kPairs * q + tid];
-    pair_epilogue<BITS>(A, I, J, n_frames, g, superpose, w_total, cutoff, radius, out, ld, sd);
+    tile_epilogue<RECT, BITS>(A, I, J, sa.n, sb.n, sa.g, sb.g, superpose, w_total, cutoff, radius, out, ld);
   } else {
     double *__restrict__ w = work + ((int64_t)ks * n_pairs + pair) * kTile;
     for (int e = tid; e < kTile; e += kBlock) w[e] = sm[e];
@@ -387,17 +458,16 @@ __global__ __launch_bounds__(kBlock, 2) void k_pw_tiles(const float *__restrict_
 
 // The n_ks partials of every A_ij entry, summed in atom-range order, then
 // the epilogue.  One workgroup per tile pair.
-template <bool BITS>
-__global__ __launch_bounds__(kBlock) void k_pw_fold(const double *__restrict__ work, int64_t n_frames,
-                                                    int64_t n_tiles, int64_t n_pairs, int64_t n_ks,
-                                                    const double *__restrict__ g, int superpose, double w_total,
-                                                    double cutoff, double radius, PairOut<BITS> *__restrict__ out,
-                                                    int64_t ld) {
-  __shared__ double sd[kTF][kTF + 1];
+template <bool RECT, bool BITS>
+__global__ __launch_bounds__(kBlock) void k_pw_fold(const double *__restrict__ work, int64_t n_a, int64_t n_b,
+                                                    int64_t tiles_b, int64_t n_pairs, int64_t n_ks,
+                                                    const double *__restrict__ g_a, const double *__restrict__ g_b,
+                                                    int superpose, double w_total, double cutoff, double radius,
+                                                    PairOut<BITS> *__restrict__ out, int64_t ld) {
   const int tid = threadIdx.x;
   const int64_t pair = blockIdx.x;
   int64_t I, J;
-  pair_to_tiles(pair, n_tiles, I, J);
+  tiles_of_pair<RECT>(pair, tiles_b, I, J);
   double A[9];
 #pragma unroll
   for (int q = 0; q < 9; ++q) {
@@ -406,196 +476,7 @@ __global__ __launch_bounds__(kBlock) void k_pw_fold(const double *__restrict__ w
     for (int64_t k = 0; k < n_ks; ++k) s += w[k * n_pairs * kTile];
     A[q] = s;
   }
-  pair_epilogue<BITS>(A, I, J, n_frames, g, superpose, w_total, cutoff, radius, out, ld, sd);
-}
-
-// ---- the rectangle: every frame of A against every frame of B ---------------
-
-static_assert(sizeof(double) * 2 * kKA * kPitch <= kLdsLimit, "the rectangle's sm fits");
-
-// One side of the rectangle: n frames at base + f fstride, their selection
-// (NULL: atoms 0..n_sel-1), centres and G.
-struct CrossSide {
-  const float *xyz;
-  int64_t fstride;
-  int64_t n;
-  const int32_t *sel;
-  const double *centre;
-  const double *g;
-};
-
-// A function of (n_a, n_b, n_sel) alone, as PwPlan is of (n_frames, n_sel).
-struct CrossPlan {
-  int64_t tiles_a, tiles_b;
-  int64_t n_pairs;   // tile pairs (I of A, J of B): pair = I tiles_b + J; 0 = more than a launch takes
-  int64_t n_ks;      // atom ranges; 1 = the epilogue runs in k_pw_cross_tiles
-  int64_t ks_atoms;  // atoms per range, a multiple of kKA
-};
-
-CrossPlan cross_plan(int64_t n_a, int64_t n_b, int64_t n_sel) {
-  CrossPlan p;
-  p.tiles_a = (n_a + kTF - 1) / kTF;
-  p.tiles_b = (n_b + kTF - 1) / kTF;
-  p.n_pairs = p.n_ks = p.ks_atoms = 0;
-  // (each factor first: the product of two int64 tile counts may not fit)
-  if (p.tiles_a > INT32_MAX || p.tiles_b > INT32_MAX || p.tiles_a * p.tiles_b > INT32_MAX) return p;
-  p.n_pairs = p.tiles_a * p.tiles_b;
-  const SplitK k = split_k(std::max<int64_t>(1, (n_sel + kKA - 1) / kKA), p.n_pairs, kTargetGroups, 1);
-  p.n_ks = k.n_ks;
-  p.ks_atoms = k.per * kKA;
-  return p;
-}
-
-size_t cross_work_doubles(const CrossPlan &p) {
-  if (p.n_ks <= 1) return 0;
-  return (size_t)p.n_ks * (size_t)p.n_pairs * kTile;
-}
-
-// Thread tid owns the pair (fi = tid >> 4 of A's tile I, fj = tid & 15 of B's
-// tile J) and its A_ij: pair_epilogue's arithmetic, one store, no mirror (fj
-// is the fastest index: the stores of 16 lanes run along a row).
-__device__ __forceinline__ void cross_epilogue(const double *A, int64_t I, int64_t J, int64_t n_a, int64_t n_b,
-                                               const double *__restrict__ g_a, const double *__restrict__ g_b,
-                                               int superpose, double w_total, double cutoff,
-                                               double *__restrict__ out, int64_t ld) {
-  const int tid = threadIdx.x;
-  const int64_t i = kTF * I + (tid >> 4), j = kTF * J + (tid & 15);
-  if (i >= n_a || j >= n_b) return;
-  out[i * ld + j] = pair_distance(A, g_a[i], g_b[j], superpose, w_total, cutoff);
-}
-
-// k_pw_tiles over the tile rectangle, each operand with a side of its own:
-// tile pair blockIdx.x = I tiles_b + J, atoms [blockIdx.y ks_atoms, ...).
-// Staging, the MFMA operands and the accumulators' meaning are k_pw_tiles';
-// operand 0 is A's tile I (times the weight), operand 1 B's tile J, both
-// always staged -- a tile of A and a tile of B are different data.  GATHER:
-// either side may have a selection (which, is the same for the whole grid).
-template <bool GATHER, bool WEIGHTED>
-__global__ __launch_bounds__(kBlock, 2) void k_pw_cross_tiles(CrossSide sa, CrossSide sb, int64_t n_sel,
-                                                           const double *__restrict__ weights, int superpose,
-                                                           double w_total, double cutoff,
-                                                           double *__restrict__ out, int64_t ld,
-                                                           double *__restrict__ work, int64_t tiles_b,
-                                                           int64_t n_pairs, int64_t ks_atoms, int direct) {
-  __shared__ double sm[2 * kKA * kPitch];  // A then B deviations; reused for the waves' sum
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int ta = tid & (kAtomLanes - 1), tf = tid >> 4;
-  const int64_t pair = blockIdx.x, ks = blockIdx.y;
-  const int64_t I = pair / tiles_b, J = pair - I * tiles_b;
-
-  const int64_t a0 = ks * ks_atoms;
-  const int64_t a1 = a0 + ks_atoms < n_sel ? a0 + ks_atoms : n_sel;
-
-  // As in k_pw_tiles: a lane past a side's last frame reads that side's last
-  // frame, an atom past the range's end the range's last atom; every load is
-  // unconditional and in bounds, and its deviation is zeroed after.
-  const float *p_op[2];
-  const int32_t *sel_op[2];
-  double cen[2][3];
-  bool live[2];
-#pragma unroll
-  for (int op = 0; op < 2; ++op) {
-    const CrossSide &sd = op ? sb : sa;
-    const int64_t f = kTF * (op ? J : I) + tf;
-    live[op] = f < sd.n;
-    const int64_t fc = live[op] ? f : sd.n - 1;
-    p_op[op] = sd.xyz + fc * sd.fstride;
-    sel_op[op] = sd.sel;
-    cen[op][0] = sd.centre[3 * fc], cen[op][1] = sd.centre[3 * fc + 1], cen[op][2] = sd.centre[3 * fc + 2];
-  }
-
-  f64x4 acc[3][3];
-  zero_3x3(acc);
-
-  const double *sA = sm;
-  const double *sB = sm + kKA * kPitch;
-
-  float raw[2][kPasses][3];
-  double wv[kPasses];
-  auto prefetch = [&](int64_t ab) {
-#pragma unroll
-    for (int pass = 0; pass < kPasses; ++pass) {
-      const int64_t a = ab + pass * kAtomLanes + ta;
-      const int64_t ac = a < a1 ? a : a1 - 1;
-      if (WEIGHTED) wv[pass] = weights[ac];
-#pragma unroll
-      for (int op = 0; op < 2; ++op) {
-        const int64_t row = 3 * (GATHER && sel_op[op] ? (int64_t)sel_op[op][ac] : ac);
-        const float *__restrict__ q = p_op[op] + row;
-        raw[op][pass][0] = q[0], raw[op][pass][1] = q[1], raw[op][pass][2] = q[2];
-      }
-    }
-  };
-  prefetch(a0);
-
-  for (int64_t ab = a0; ab < a1; ab += kKA) {
-    // ---- stage kKA atoms of both operand tiles (zeros past either edge)
-#pragma unroll
-    for (int op = 0; op < 2; ++op) {
-#pragma unroll
-      for (int pass = 0; pass < kPasses; ++pass) {
-        const int k = pass * kAtomLanes + ta;
-        const bool on = live[op] && ab + k < a1;
-        double d0 = on ? (double)raw[op][pass][0] - cen[op][0] : 0.0;
-        double d1 = on ? (double)raw[op][pass][1] - cen[op][1] : 0.0;
-        double d2 = on ? (double)raw[op][pass][2] - cen[op][2] : 0.0;
-        if (WEIGHTED && op == 0) d0 *= wv[pass], d1 *= wv[pass], d2 *= wv[pass];
-        double *__restrict__ o = sm + (op * kKA + k) * kPitch + tf;
-        o[0] = d0, o[kTF] = d1, o[2 * kTF] = d2;
-      }
-    }
-    __syncthreads();
-    // (after the barrier: its fence waits for every load in flight)
-    if (ab + kKA < a1) prefetch(ab + kKA);
-    // ---- contract: wave w takes atoms [8 w, 8 w + 8) of the staged tile
-#pragma unroll
-    for (int s = 0; s < kKA / (4 * kWaves); ++s) {
-      const int k = (kKA / kWaves) * wave + 4 * s + (lane >> 4);
-      const double *__restrict__ ra = sA + k * kPitch + (lane & 15);
-      const double *__restrict__ rb = sB + k * kPitch + (lane & 15);
-      const double x0 = ra[0], x1 = ra[kTF], x2 = ra[2 * kTF];
-      const double y0 = rb[0], y1 = rb[kTF], y2 = rb[2 * kTF];
-      mfma_3x3(acc, x0, x1, x2, y0, y1, y2);
-    }
-    __syncthreads();
-  }
-
-  wave_sum_3x3(acc, sm, lane, wave,
-               [](int i, int j, int row, int col) { return kPairs * (3 * i + j) + kTF * row + col; });
-
-  if (direct) {
-    double A[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) A[q] = sm[kPairs * q + tid];
-    cross_epilogue(A, I, J, sa.n, sb.n, sa.g, sb.g, superpose, w_total, cutoff, out, ld);
-  } else {
-    double *__restrict__ w = work + ((int64_t)ks * n_pairs + pair) * kTile;
-    for (int e = tid; e < kTile; e += kBlock) w[e] = sm[e];
-  }
-}
-
-// The n_ks partials of every A_ij entry, summed in atom-range order, then
-// the epilogue.  One workgroup per tile pair.
-__global__ __launch_bounds__(kBlock) void k_pw_cross_fold(const double *__restrict__ work, int64_t n_a, int64_t n_b,
-                                                          int64_t tiles_b, int64_t n_pairs, int64_t n_ks,
-                                                          const double *__restrict__ g_a,
-                                                          const double *__restrict__ g_b, int superpose,
-                                                          double w_total, double cutoff, double *__restrict__ out,
-                                                          int64_t ld) {
-  const int tid = threadIdx.x;
-  const int64_t pair = blockIdx.x;
-  const int64_t I = pair / tiles_b, J = pair - I * tiles_b;
-  double A[9];
-#pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    const double *__restrict__ w = work + pair * kTile + kPairs * q + tid;
-    double s = 0.0;
-    for (int64_t k = 0; k < n_ks; ++k) s += w[k * n_pairs * kTile];
-    A[q] = s;
-  }
-  cross_epilogue(A, I, J, n_a, n_b, g_a, g_b, superpose, w_total, cutoff, out, ld);
+  tile_epilogue<RECT, BITS>(A, I, J, n_a, n_b, g_a, g_b, superpose, w_total, cutoff, radius, out, ld);
 }
 
 // One workgroup per row of m[n_rows][ld]: its least entry and that entry's
@@ -659,31 +540,29 @@ int launch_centres(const char *who, const float *d_xyz, int64_t fstride, int64_t
 }
 
 // k_pw_tiles and, with more than one atom range, k_pw_fold over every tile
-// pair of n_frames frames, storing distances (out f64 [n][ld]) or, BITS, the
-// neighbour bits within `radius` (out uint16 [n][ld], ld in 16-bit elements).
+// pair of the plan: of the square of side sa (sb the same), storing distances
+// (out f64 [n][ld]) or, BITS, the neighbour bits within `radius` (out uint16
+// [n][ld], ld in 16-bit elements), or, RECT, of the rectangle sa x sb.
 // Everything that can be refused is refused before the first launch; the
 // pointers and sizes that do not depend on the plan are the caller's, already
 // checked, and `who` names it in the messages.
-template <bool BITS>
-int launch_pairs(const char *who, const float *d_xyz, int64_t fstride, int64_t n_frames, int64_t n_sel,
-                 const int32_t *d_sel, const double *d_weights, double w_total, const double *d_centre,
-                 const double *d_g, int superpose, double cutoff, double radius, PairOut<BITS> *d_out, int64_t ld,
-                 void *d_work, size_t work_bytes, void *stream) {
-  if (n_frames == 0) return RMSF_OK;
-  const PwPlan pl = pw_plan(n_frames, n_sel);
-  if (pl.n_pairs > INT32_MAX || pl.n_ks > 65535)
+template <bool RECT, bool BITS>
+int launch_tiles(const char *who, const TilePlan &pl, const Side &sa, const Side &sb, int64_t n_sel,
+                 const double *d_weights, double w_total, int superpose, double cutoff, double radius,
+                 PairOut<BITS> *d_out, int64_t ld, void *d_work, size_t work_bytes, void *stream) {
+  if (pl.n_pairs == 0 || pl.n_pairs > INT32_MAX || pl.n_ks > 65535)
     return fail(RMSF_EINVAL, std::string(who) + ": too many frames for one launch");
-  const size_t need = pw_work_doubles(pl) * sizeof(double);
+  const size_t need = work_doubles(pl) * sizeof(double);
   if (need && (!d_work || work_bytes < need)) return fail(RMSF_ENOMEM, std::string(who) + ": workspace too small");
   const int direct = pl.n_ks == 1;
   double *work = static_cast<double *>(d_work);
   const dim3 block(kBlock);
-#define PW_LAUNCH(G_, W_)                                                                                      \
-  hipLaunchKernelGGL((k_pw_tiles<G_, W_, BITS>), grid, block, 0, S(stream), d_xyz, fstride, n_frames, n_sel,   \
-                     d_sel, d_weights, d_centre, d_g, superpose, w_total, cutoff, radius, d_out, ld, work,     \
-                     pl.n_tiles, pl.n_pairs, pl.ks_atoms, direct, p0)
-  const bool gt = d_sel != nullptr, wt = d_weights != nullptr;
-  // kMaxGroups tile pairs a launch (past 352 frames there is one atom range, and below there is one launch)
+#define PW_LAUNCH(G_, W_)                                                                                       \
+  hipLaunchKernelGGL((k_pw_tiles<G_, W_, RECT, BITS>), grid, block, 0, S(stream), sa, sb, n_sel, d_weights,      \
+                     superpose, w_total, cutoff, radius, d_out, ld, work, pl.tiles_b, pl.n_pairs, pl.ks_atoms, \
+                     direct, p0)
+  const bool gt = sa.sel != nullptr || sb.sel != nullptr, wt = d_weights != nullptr;
+  // kMaxGroups tile pairs a launch (past 256 tile pairs there is one atom range, and below there is one launch)
   for (int64_t p0 = 0; p0 < pl.n_pairs; p0 += kMaxGroups) {
     const dim3 grid((unsigned)std::min<int64_t>(kMaxGroups, pl.n_pairs - p0), (unsigned)pl.n_ks);
     if (gt && wt) PW_LAUNCH(true, true);
@@ -694,11 +573,23 @@ int launch_pairs(const char *who, const float *d_xyz, int64_t fstride, int64_t n
   }
 #undef PW_LAUNCH
   if (!direct) {
-    hipLaunchKernelGGL(k_pw_fold<BITS>, dim3((unsigned)pl.n_pairs), block, 0, S(stream), work, n_frames, pl.n_tiles,
-                       pl.n_pairs, pl.n_ks, d_g, superpose, w_total, cutoff, radius, d_out, ld);
+    hipLaunchKernelGGL((k_pw_fold<RECT, BITS>), dim3((unsigned)pl.n_pairs), block, 0, S(stream), work, sa.n, sb.n,
+                       pl.tiles_b, pl.n_pairs, pl.n_ks, sa.g, sb.g, superpose, w_total, cutoff, radius, d_out, ld);
     if (int rc = after_launch("k_pw_fold")) return rc;
   }
   return RMSF_OK;
+}
+
+// launch_tiles over the square of one trajectory's frames.
+template <bool BITS>
+int launch_pairs(const char *who, const float *d_xyz, int64_t fstride, int64_t n_frames, int64_t n_sel,
+                 const int32_t *d_sel, const double *d_weights, double w_total, const double *d_centre,
+                 const double *d_g, int superpose, double cutoff, double radius, PairOut<BITS> *d_out, int64_t ld,
+                 void *d_work, size_t work_bytes, void *stream) {
+  if (n_frames == 0) return RMSF_OK;
+  const Side s{d_xyz, fstride, n_frames, d_sel, d_centre, d_g};
+  return launch_tiles<false, BITS>(who, pw_plan(n_frames, n_sel), s, s, n_sel, d_weights, w_total, superpose, cutoff,
+                                   radius, d_out, ld, d_work, work_bytes, stream);
 }
 
 }  // namespace
@@ -725,7 +616,7 @@ RMSF_EXPORT int rmsf_pairwise_centres_about(const float *d_xyz, int64_t fstride,
 
 RMSF_EXPORT size_t rmsf_pairwise_workspace_bytes(int64_t n_frames, int64_t n_sel) {
   if (n_sel < 1 || n_frames < 1) return 0;
-  return pw_work_doubles(pw_plan(n_frames, n_sel)) * sizeof(double);
+  return work_doubles(pw_plan(n_frames, n_sel)) * sizeof(double);
 }
 
 RMSF_EXPORT int rmsf_pairwise_rmsd(const float *d_xyz, int64_t fstride, int64_t n_frames, int64_t n_sel,
@@ -758,7 +649,7 @@ RMSF_EXPORT int rmsf_pairwise_adjacency(const float *d_xyz, int64_t fstride, int
 
 RMSF_EXPORT size_t rmsf_cross_workspace_bytes(int64_t n_a, int64_t n_b, int64_t n_sel) {
   if (n_sel < 1 || n_a < 1 || n_b < 1) return 0;
-  return cross_work_doubles(cross_plan(n_a, n_b, n_sel)) * sizeof(double);
+  return work_doubles(cross_plan(n_a, n_b, n_sel)) * sizeof(double);
 }
 
 RMSF_EXPORT int rmsf_cross_rmsd(const float *d_a, int64_t stride_a, int64_t n_a, const int32_t *d_sel_a,
@@ -771,32 +662,10 @@ RMSF_EXPORT int rmsf_cross_rmsd(const float *d_a, int64_t stride_a, int64_t n_a,
       stride_a < 0 || stride_b < 0 || ld < n_b || !(w_total > 0.0))
     return fail(RMSF_EINVAL, "rmsf_cross_rmsd: bad arguments");
   if (n_a == 0 || n_b == 0) return RMSF_OK;
-  const CrossPlan pl = cross_plan(n_a, n_b, n_sel);
-  if (pl.n_pairs == 0 || pl.n_ks > 65535)
-    return fail(RMSF_EINVAL, "rmsf_cross_rmsd: too many frames for one launch");
-  const size_t need = cross_work_doubles(pl) * sizeof(double);
-  if (need && (!d_work || work_bytes < need)) return fail(RMSF_ENOMEM, "rmsf_cross_rmsd: workspace too small");
-  const int direct = pl.n_ks == 1;
-  double *work = static_cast<double *>(d_work);
-  const CrossSide sa{d_a, stride_a, n_a, d_sel_a, d_centre_a, d_g_a};
-  const CrossSide sb{d_b, stride_b, n_b, d_sel_b, d_centre_b, d_g_b};
-  const dim3 grid((unsigned)pl.n_pairs, (unsigned)pl.n_ks), block(kBlock);
-#define CROSS_LAUNCH(G_, W_)                                                                                    \
-  hipLaunchKernelGGL((k_pw_cross_tiles<G_, W_>), grid, block, 0, S(stream), sa, sb, n_sel, d_weights, superpose, \
-                     w_total, cutoff, d_out, ld, work, pl.tiles_b, pl.n_pairs, pl.ks_atoms, direct)
-  const bool gt = d_sel_a != nullptr || d_sel_b != nullptr, wt = d_weights != nullptr;
-  if (gt && wt) CROSS_LAUNCH(true, true);
-  else if (gt) CROSS_LAUNCH(true, false);
-  else if (wt) CROSS_LAUNCH(false, true);
-  else CROSS_LAUNCH(false, false);
-#undef CROSS_LAUNCH
-  if (int rc = after_launch("k_pw_cross_tiles")) return rc;
-  if (!direct) {
-    hipLaunchKernelGGL(k_pw_cross_fold, dim3((unsigned)pl.n_pairs), block, 0, S(stream), work, n_a, n_b, pl.tiles_b,
-                       pl.n_pairs, pl.n_ks, d_g_a, d_g_b, superpose, w_total, cutoff, d_out, ld);
-    if (int rc = after_launch("k_pw_cross_fold")) return rc;
-  }
-  return RMSF_OK;
+  const Side sa{d_a, stride_a, n_a, d_sel_a, d_centre_a, d_g_a};
+  const Side sb{d_b, stride_b, n_b, d_sel_b, d_centre_b, d_g_b};
+  return launch_tiles<true, false>("rmsf_cross_rmsd", cross_plan(n_a, n_b, n_sel), sa, sb, n_sel, d_weights, w_total,
+                                   superpose, cutoff, 0.0, d_out, ld, d_work, work_bytes, stream);
 }
 
 RMSF_EXPORT int rmsf_row_argmin(const double *d_m, int64_t n_rows, int64_t n_cols, int64_t ld, int64_t *d_idx,

@@ -352,7 +352,7 @@ class CrossDistanceMatrix:
     RMSD of every frame to a set of reference structures, the 2-D RMSD plot
     between two runs, the input of ``hausdorff`` and ``discrete_frechet``.
     Only the F_a x F_b pairs asked for are computed (csrc/pairwise.hip,
-    ``k_pw_cross_tiles``), each once.
+    ``k_pw_tiles`` over the tile rectangle), each once.
 
     Parameters
     ----------

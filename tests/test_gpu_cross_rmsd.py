@@ -1,5 +1,5 @@
 """GPU tier: the cross RMSD matrix d[i, j] = RMSD(A_i, B_j) (csrc/pairwise.hip,
-``k_pw_cross_tiles`` / ``k_pw_cross_fold``), ``rmsf_row_argmin`` and
+the rectangle's ``k_pw_tiles`` / ``k_pw_fold``), ``rmsf_row_argmin`` and
 ``CrossDistanceMatrix``, against a numpy f64 reference that does not use QCP:
 
   * superposition on: weighted centring of either side, ``H = (w d_Bj)^T
@@ -554,3 +554,59 @@ def test_matrix_over_half_the_free_hbm_is_refused():
     x = torch.zeros((200_000, 3, 3), dtype=torch.float32, device="cuda:0")
     with pytest.raises(MemoryError, match=str(8 * 200_000 ** 2)):
         CrossDistanceMatrix(x, x).run()
+
+
+# ---- more tile pairs than one launch takes ---------------------------------------------------
+def test_more_tile_pairs_than_a_launch_takes():
+    """65,537 x 65,536 frames are 4,097 x 4,096 = 2^24 + 4,096 tile pairs; 2^32 / 256 = 2^24 workgroups is what
+    one launch runs in full (a larger grid is not refused: its count wraps), so this is the smallest rectangle
+    past the wrap, with a one-frame last tile row.  Five 4-atom structures on a 2^-10 A grid, each frame of A
+    and of B one of them moved by a translation on that grid: coordinates, centres (a quotient by 4) and
+    deviations are exact, so the deviations of two frames of one structure are the same bits and out[i, j] is a
+    function of (state_a[i], state_b[j]) alone -- the 5 x 5 matrix T of the structures against themselves, one
+    tile, itself held against numpy f64."""
+    import torch
+
+    from rmsf_amd.engine import Engine
+    from test_gpu_pairwise import BOUND as SQUARE_BOUND
+    from test_gpu_pairwise import reference_sq as square_reference_sq
+    n_a, n_b, n_sel, n_states = 65_537, 65_536, 4, 5
+    assert (-(-n_a // 16)) * (-(-n_b // 16)) > 2 ** 32 // 256
+    need = 48e9   # the 34.4 GB matrix, the 0.5 GB row-block temporaries, and room to spare
+    free = torch.cuda.mem_get_info()[0]
+    if free < need:
+        pytest.skip(f"{free / 1e9:.1f} GB of HBM are free, the 65,537 x 65,536 matrix and its check need 48 GB")
+    rng = np.random.default_rng(65_537)
+    base = (rng.integers(0, 16 * 1024, size=(n_states, n_sel, 3)) / 1024.0).astype(np.float32)
+    state_a, state_b = rng.integers(0, n_states, size=n_a), rng.integers(0, n_states, size=n_b)
+
+    def moved(state):
+        shift = rng.integers(-8 * 1024, 8 * 1024 + 1, size=(len(state), 1, 3)) / 1024.0
+        x = base[state].astype(np.float64) + shift
+        assert np.array_equal(x.astype(np.float32).astype(np.float64), x)           # exact in f32
+        return x.astype(np.float32)
+
+    xa, xb = moved(state_a), moved(state_b)
+    t = engine_cross(base, None, base, None, None, True, cutoff=1e-5)
+    sq, s = square_reference_sq(base, None, True)
+    ratio = np.abs(t * t - sq) / (SQUARE_BOUND * s)
+    print(f"T (5 x 5): max |d2 - d2_ref| / (1e-12 S) = {ratio.max():.3e}")
+    assert ratio.max() <= 1.0
+    off = ~np.eye(n_states, dtype=bool)
+    assert np.sqrt(np.abs(sq[off])).min() > 1.0 and t[off].min() > 1.0     # different structures are far apart
+    assert np.all(np.diag(t) == 0.0)
+
+    eng = Engine(torch.device("cuda", 0))
+    assert eng.cross_workspace_bytes(n_a, n_b, n_sel) == 0
+    ta, tb = torch.tensor(xa, device="cuda:0"), torch.tensor(xb, device="cuda:0")
+    ca, ga = eng.pairwise_centres(ta.data_ptr(), ta.stride(0), n_a, n_sel, None, None, True)
+    cb, gb = eng.pairwise_centres(tb.data_ptr(), tb.stride(0), n_b, n_sel, None, None, True)
+    out = torch.full((n_a + 1, n_b + 1), float("nan"), dtype=torch.float64, device="cuda:0")
+    eng.cross_rmsd(ta.data_ptr(), ta.stride(0), n_a, None, ca, ga, tb.data_ptr(), tb.stride(0), n_b, None, cb, gb,
+                   n_sel, None, float(n_sel), out, superpose=True, cutoff=1e-5)
+    t_dev = torch.tensor(t, device="cuda:0")
+    sa_dev, sb_dev = torch.tensor(state_a, device="cuda:0"), torch.tensor(state_b, device="cuda:0")
+    for r0 in range(0, n_a, 1024):
+        r1 = min(r0 + 1024, n_a)
+        assert torch.equal(out[r0:r1, :n_b], t_dev[sa_dev[r0:r1]][:, sb_dev]), f"rows {r0}..{r1 - 1}"
+    assert bool(torch.isnan(out[n_a]).all()) and bool(torch.isnan(out[:, n_b]).all())

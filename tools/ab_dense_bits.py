@@ -7,8 +7,10 @@ checkouts (a refactor's proof: csrc/dense_f64.h, rmsf_device.h::qcp_lambda).
 
 ``dump`` imports rmsf_amd from the checkout at PATH (built there), runs seeded
 inputs through its ``Engine`` and saves the raw outputs: covariance
-(accumulate + finish), pairwise RMSD (centres + rmsd, cutoff 0), pca_project,
-qcp_batch, and the transform records of superpose and superpose_seq.
+(accumulate + finish), pairwise RMSD (centres + rmsd, cutoff 0), its neighbour
+bits and counts (pairwise_adjacency within the median distance), the cross RMSD
+matrix (centres per side + cross_rmsd, cutoff 0), pca_project, qcp_batch, and
+the transform records of superpose and superpose_seq.
 ``compare`` demands the same arrays with the same uint64 views; exit status 1
 on any difference.  One process per dump: two checkouts' packages cannot share
 an interpreter.
@@ -22,6 +24,8 @@ import numpy as np
 
 COV_SHAPES = [(5, 3), (17, 5), (214, 67), (341, 300), (500, 40)]                  # (n_sel, n_frames)
 PW_SHAPES = [(2, 3), (17, 33), (33, 31), (50, 214), (5, 5000), (500, 40)]         # (n_frames, n_sel)
+ADJ_SHAPES = PW_SHAPES + [(130, 20), (300, 50)]                                   # (n_frames, n_sel)
+CROSS_SHAPES = [(1, 1, 3), (17, 33, 33), (33, 5, 31), (3, 5, 5000), (50, 40, 214), (528, 130, 40)]  # (n_a, n_b, n_sel)
 # tests/test_gpu_pca_project.py::ENGINE_SHAPES as (n_sel, n_frames, k)
 PROJ_SHAPES = [(1, 1, 1), (5, 3, 2), (16, 16, 16), (17, 17, 17), (17, 33, 51), (214, 67, 10), (341, 300, 7),
                (5000, 5, 3)]
@@ -97,6 +101,62 @@ def dump(tree, out_path):
                           cutoff=0.0, work=work)
         key = f"pw_{n_frames}x{n_sel}_g{int(gathered)}_w{int(weighted)}_s{int(superpose)}"
         out[key + "_centre"], out[key + "_g"], out[key] = centre.cpu().numpy(), g.cpu().numpy(), d.cpu().numpy()
+
+    # the neighbour bits of the same cases (and two shapes more) within the median off-diagonal distance
+    for (n_frames, n_sel), gathered, weighted, superpose in itertools.product(ADJ_SHAPES, (False, True),
+                                                                               (False, True), (True, False)):
+        x, sel_dev = case(n_sel, n_frames, gathered)
+        w = np.random.default_rng(n_sel).uniform(1.0, 16.0, size=n_sel) if weighted else None
+        w_dev = None if w is None else torch.tensor(w, device=dev)
+        w_total = float(n_sel) if w is None else float(w.sum())
+        centre, g = eng.pairwise_centres(x.data_ptr(), x.stride(0), n_frames, n_sel, sel_dev, w_dev, superpose)
+        need = eng.pairwise_workspace_bytes(n_frames, n_sel)
+        work = eng.empty(need // 8) if need else None
+        tag = f"{n_frames}x{n_sel}_g{int(gathered)}_w{int(weighted)}_s{int(superpose)}"
+        d = out.get("pw_" + tag)
+        if d is None:  # a shape without a pw_ array: the same matrix, for the radius alone
+            d = eng.empty(n_frames, n_frames)
+            eng.pairwise_rmsd(x.data_ptr(), x.stride(0), n_frames, n_sel, sel_dev, w_dev, w_total, centre, g, d,
+                              superpose=superpose, cutoff=0.0, work=work)
+            d = d.cpu().numpy()
+        radius = float(np.median(d[~np.eye(n_frames, dtype=bool)]))
+        adj = torch.full((n_frames, eng.adjacency_words(n_frames)), -1, dtype=torch.int64, device=dev)
+        count = torch.full((n_frames,), -1, dtype=torch.int32, device=dev)
+        eng.pairwise_adjacency(x.data_ptr(), x.stride(0), n_frames, n_sel, sel_dev, w_dev, w_total, centre, g, adj,
+                               count, radius, superpose=superpose, zero_cutoff=0.0, work=work)
+        out["adj_" + tag], out["adj_" + tag + "_count"] = adj.cpu().numpy(), count.cpu().numpy().astype(np.int64)
+        out["adj_" + tag + "_radius"] = np.asarray([radius])
+
+    for (n_a, n_b, n_sel), (ga_, gb_), weighted, superpose in itertools.product(
+            CROSS_SHAPES, ((False, False), (True, False), (False, True), (True, True)), (False, True), (True, False)):
+        # one seeded trajectory, A its first n_a frames and B the rest, as selected rows: each side dense, or
+        # scattered over 3 n_sel atoms and gathered back
+        rows = trajectory(n_sel, n_a + n_b)
+
+        def side(xs, gathered):
+            n_atoms, sel = selection(n_sel, gathered)
+            full = np.zeros((len(xs), n_atoms, 3), dtype=np.float32)
+            full[:, slice(None) if sel is None else sel] = xs
+            return torch.tensor(full, device=dev), eng.sel_tensor(sel)
+
+        (xa, sel_a), (xb, sel_b) = side(rows[:n_a], ga_), side(rows[n_a:], gb_)
+        w = np.random.default_rng(n_sel).uniform(1.0, 16.0, size=n_sel) if weighted else None
+        w_dev = None if w is None else torch.tensor(w, device=dev)
+        ca, g_a = eng.pairwise_centres(xa.data_ptr(), xa.stride(0), n_a, n_sel, sel_a, w_dev, superpose)
+        if superpose:
+            cb, g_b = eng.pairwise_centres(xb.data_ptr(), xb.stride(0), n_b, n_sel, sel_b, w_dev, True)
+        else:  # one common origin, A's frame 0's centre: what CrossDistanceMatrix.run does
+            cb, g_b = eng.pairwise_centres_about(xb.data_ptr(), xb.stride(0), n_b, n_sel, sel_b, w_dev, ca)
+        need = eng.cross_workspace_bytes(n_a, n_b, n_sel)
+        work = eng.empty(need // 8) if need else None
+        d = torch.full((n_a, n_b), float("nan"), dtype=torch.float64, device=dev)
+        eng.cross_rmsd(xa.data_ptr(), xa.stride(0), n_a, sel_a, ca, g_a, xb.data_ptr(), xb.stride(0), n_b, sel_b,
+                       cb, g_b, n_sel, w_dev, float(n_sel) if w is None else float(w.sum()), d, superpose=superpose,
+                       cutoff=0.0, work=work)
+        key = f"cross_{n_a}x{n_b}x{n_sel}_ga{int(ga_)}_gb{int(gb_)}_w{int(weighted)}_s{int(superpose)}"
+        out[key] = d.cpu().numpy()
+        out[key + "_centre_a"], out[key + "_g_a"] = ca.cpu().numpy(), g_a.cpu().numpy()
+        out[key + "_centre_b"], out[key + "_g_b"] = cb.cpu().numpy(), g_b.cpu().numpy()
 
     for (n_sel, n_frames, k), gathered, aligned in itertools.product(PROJ_SHAPES, (False, True), (False, True)):
         x, sel_dev = case(n_sel, n_frames, gathered)

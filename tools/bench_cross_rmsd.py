@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Timing of the cross RMSD matrix d[i, j] = RMSD(A_i, B_j) (csrc/pairwise.hip,
-k_pw_cross_tiles) on one MI355X.
+k_pw_tiles over the tile rectangle) on one MI355X.
 
 Per shape (frames of A x frames of B x selected atoms, HBM-resident f32 rows),
 device events per repetition after two warm-up repetitions, median / min / max
