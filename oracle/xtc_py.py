@@ -4,7 +4,11 @@ An independent restatement (Python integers, no shared code) of the published
 xdrfile xdr3dfcoord decompression, used to cross-check the native reader in
 csrc/xtc.cpp.  MDAnalysis' XTCReader (libxdrfile, not vendored in
 /root/reference and not installed here) is the upstream this mirrors; no
-real XTC file exists in this environment, so the format itself is UNPINNED.
+real XTC file exists in this environment.  For the decoders (this one
+included) the format is pinned by construction: tests/xtc_streams.py encodes
+streams group by group from explicit integers, and tests/test_xtc_streams.py
+holds every decoder to those integers.  The writer (write_xtc) is still
+UNPINNED: it is checked by round trip only.
 """
 from __future__ import annotations
 

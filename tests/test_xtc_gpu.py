@@ -7,7 +7,15 @@ raw (<= 9 atoms), runs + water swap, packed triples wider than 52 bits (byte
 long division), per-axis bit sizes (large range) and small-integer indices
 up to the end of the magicints table; corrupt records are rejected.
 GPU tier: the device kernel and the pinned-slot decoder give the same bytes,
-and RMSF from a GPU-decoded XTC equals RMSF from the host-decoded one."""
+and RMSF from a GPU-decoded XTC equals RMSF from the host-decoded one.
+
+Every stream here comes from the project's own writer and every reference is
+another decoder.  tests/test_xtc_streams.py (CPU tier) and
+tests/test_gpu_xtc_streams.py (GPU tier) decode streams built group by group
+in plain Python (tests/xtc_streams.py) against the integers that went in:
+what the writer never produces (53..72-bit small triples in runs, runs of 9
+and 10, chosen stream lengths and stretches of clean groups around the
+device's stage, ring and batch sizes) and streams broken in one known place."""
 
 import numpy as np
 import pytest
