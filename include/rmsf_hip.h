@@ -659,6 +659,32 @@ int rmsf_block_update(double alpha, const double *d_a, int64_t lda,
                       const double *d_t, int64_t ldt, int64_t n, int64_t nc,
                       double *d_c, int64_t ldc, void *stream);
 
+/* ---- diffusion kernel of a distance matrix (DiffusionMap(solver="device")) --
+ * rmsf_diffusion_kernel: in one pass over d_m[n][ld] (f64, ld >= n, in HBM)
+ *   every distance d becomes exp(-(d * d) / epsilon) in place, and d_rowsum[r]
+ *   receives the sum of row r's n new values (csrc/diffusion.hip): 8 n^2 bytes
+ *   read, 8 n^2 written.  The argument is formed as written, with a true f64
+ *   division, so it has the bits numpy gives it and only the two exp can
+ *   differ.  d = 0 gives exactly 1; d = +-inf, or an argument below exp's
+ *   underflow point, exactly 0; a NaN stays NaN and makes its row's sum NaN.
+ *   The transform is element-wise: a matrix symmetric in its bits stays so
+ *   (rmsf_symm_block's precondition).  Columns n..ld-1 are neither read nor
+ *   written.  A row's sum has a fixed order -- each lane's terms in column
+ *   order, the 64 lanes by a halving tree, the waves in order -- and no
+ *   atomics: the same bits on every run.  Rows that are all 16-byte aligned
+ *   (d_m is, and ld is even) are moved 16 bytes a lane, others 8; the two
+ *   forms sum in different orders.  n <= INT32_MAX.  A NULL pointer, n < 1,
+ *   ld < n, an epsilon that is not positive and finite: RMSF_EINVAL.
+ * rmsf_block_scale_rows:  d_c[r * ldc + c] = d_s[r] d_a[r * lda + c] for r < n,
+ *   c < nc <= 48: C = diag(s) A for a block of the eigen-solver, one multiply
+ *   an element.  d_c may be d_a.  A NULL pointer, a size < 1, more than 48
+ *   columns, lda or ldc < nc: RMSF_EINVAL.                                    */
+int rmsf_diffusion_kernel(double *d_m, int64_t ld, int64_t n, double epsilon,
+                          double *d_rowsum, void *stream);
+int rmsf_block_scale_rows(const double *d_s, const double *d_a, int64_t lda,
+                          int64_t n, int64_t nc, double *d_c, int64_t ldc,
+                          void *stream);
+
 /* ---- all-pairs RMSD matrix (MDAnalysis.analysis.diffusionmap.DistanceMatrix)
  * The n_frames x n_frames matrix of RMSDs between every pair of frames of a
  * batch read at a constant frame_stride, on the f64 matrix cores

@@ -14,7 +14,9 @@ Public surface (mirrors the reference's names):
     ``PCA(solver="matrix_free")`` finds them from the trajectory with no [3n, 3n] matrix at all;
     ``rmsip`` / ``cumulative_overlap`` compare two sets of modes
   * ``DistanceMatrix`` / ``DiffusionMap`` -- the all-pairs RMSD matrix of the frames and
-    its diffusion map, named as MDAnalysis.analysis.diffusionmap names them
+    its diffusion map, named as MDAnalysis.analysis.diffusionmap names them;
+    ``DiffusionMap(DistanceMatrix(traj), epsilon, n_eigenvectors=k, solver="device")`` finds the first k
+    diffusion coordinates with the matrix and its kernel kept in HBM (``rmsf_amd.eigen.KernelOps``)
   * ``CrossDistanceMatrix`` -- the rectangular RMSD matrix of every frame of one trajectory to
     every frame of another (or to a set of references) and each frame's nearest reference;
     ``hausdorff`` / ``discrete_frechet`` -- the path distances of such a matrix, named as

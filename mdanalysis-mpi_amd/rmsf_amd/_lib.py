@@ -116,6 +116,8 @@ SIGNATURES = {
     "rmsf_block_gram": (c_int, [P, c_int64, c_int64, P, c_int64, c_int64, c_int64, P, c_int64, P, c_size_t, P]),
     "rmsf_block_update": (c_int, [c_double, P, c_int64, P, c_int64, c_int64, P, c_int64, c_int64, c_int64, P, c_int64,
                                   P]),
+    "rmsf_diffusion_kernel": (c_int, [P, c_int64, c_int64, c_double, P, P]),
+    "rmsf_block_scale_rows": (c_int, [P, P, c_int64, c_int64, c_int64, P, c_int64, P]),
     "rmsf_pairwise_centres": (c_int,[P, c_int64, c_int64, c_int64, P, P, c_int, P, P, P]),
     "rmsf_pairwise_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "rmsf_pairwise_rmsd": (c_int, [P, c_int64, c_int64, c_int64, P, P, c_double, P, P, c_int, c_double, P, c_int64, P,

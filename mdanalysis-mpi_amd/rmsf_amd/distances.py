@@ -10,7 +10,9 @@ and each pair's RMSD comes from the QCP quartic's largest root in the same
 kernel -- no rotation, no 9 F^2 intermediate, every pair once.
 
 ``DiffusionMap`` is the eigen-decomposition of the diffusion kernel of that
-matrix, on the host (numpy only, like ``pca_from_comoment``).
+matrix: on the host (numpy only, like ``pca_from_comoment``), or, with
+``solver="device"``, its first modes with the matrix kept in HBM
+(csrc/diffusion.hip and the block solver of ``rmsf_amd.eigen``).
 
 ``CrossDistanceMatrix(a, b).run().results.dist_matrix`` is the rectangular
 F_a x F_b matrix of the RMSDs of every frame of one trajectory to every frame
@@ -31,6 +33,7 @@ import numpy as np
 import torch
 
 from . import parallel
+from .eigen import MAX_COMPONENTS, KernelOps, block_width, top_eigenpairs
 from .engine import Engine
 from .rms import Results, make_source
 from .sources import DeviceSource, FrameList
@@ -553,17 +556,164 @@ class DiffusionMap:
     right eigenvectors of P as columns (the first constant).  P is solved
     through its symmetric conjugate ``D^-1/2 K D^-1/2`` with
     ``numpy.linalg.eigh``, so the spectrum is real: P's right eigenvectors
-    are ``D^-1/2`` times the conjugate's.  Host only, numpy only.
+    are ``D^-1/2`` times the conjugate's.  ``solver="host"`` (the default) is
+    that: host only, numpy only, all F eigenpairs at O(F^3);
+    ``n_eigenvectors`` and the solver's parameters are ignored.
+
+    ``solver="device"``: the first ``n_eigenvectors`` = k diffusion
+    coordinates (1 <= k <= 39) and the constant mode before them, with the
+    matrix in HBM from start to end.  ``dist`` may then be
+
+      * a ``DistanceMatrix`` that has not run -- any trajectory input, wrapped:
+        ``DiffusionMap(DistanceMatrix(ca), ...)``.  Its matrix is computed in
+        HBM, transformed in place and never copied to the host (its
+        ``results.dist_matrix`` stays unset); memory and refusals are
+        ``DistanceMatrix``'s own.
+      * a ``DistanceMatrix`` that has run, or a host [F, F] array: uploaded.
+      * a square f64 HBM tensor: copied, the caller's stays as it is; a copy
+        over half the free HBM is a MemoryError.
+
+    A matrix of the caller's must be exactly symmetric, ``d[i, j] == d[j, i]``:
+    the device product reads K[j, i] where the formula has K[i, j].  The host
+    path symmetrises the conjugate matrix and forgives a rounding's difference;
+    here the kernel of such a matrix is compared with its transpose once on
+    the device and a difference is a ValueError (pass ``0.5 * (d + d.T)``).
+
+    One pass (csrc/diffusion.hip) turns the distances into K and sums its
+    rows; the F row sums come to the host, and one that is not positive and
+    finite -- a NaN distance, a user's matrix whose diagonal underflows -- is a
+    ValueError.  ``rmsf_amd.eigen.top_eigenpairs`` then runs over
+    ``KernelOps``: ``symm(Q) = D^-1/2 K (D^-1/2 Q)``, K read once per
+    iteration on the f64 matrix cores, the conjugate never written.
+    ``results.eigenvalues`` [k + 1] descending, the first 1 to the solver's
+    tolerance; ``results.eigenvectors`` [F, k + 1] host f64, ``D^-1/2`` times
+    the conjugate's orthonormal vectors, the constant one positive;
+    ``results.solver_info`` the driver's record (``tol``, ``max_iter``,
+    ``seed`` are its parameters).  ``PCAConvergenceError`` when it does not
+    converge; ValueError for a bad k or solver before any device work, and
+    for k + 1 > F as soon as F is known, before the matrix is computed.
+
+    The Gaussian kernel of superposed RMSDs is not guaranteed positive
+    semi-definite: minimal RMSD is not a Euclidean distance.  The driver
+    returns the largest eigenvalues of the subspace it finds, which for the
+    spectra met here are the leading ones; a matrix with a negative eigenvalue
+    of large magnitude would draw the iteration towards it.  Modes in a flat
+    tail of the spectrum crawl, as they do for ``PCA(solver="device")``: ask
+    for fewer, or raise ``max_iter``.
     """
 
-    def __init__(self, dist, epsilon: float = 1.0):
+    MAX_EIGENVECTORS = MAX_COMPONENTS - 1  # the constant mode is computed with the others
+
+    def __init__(self, dist, epsilon: float = 1.0, *, n_eigenvectors: int | None = None, solver: str = "host",
+                 tol: float = 1e-10, max_iter: int = 300, seed: int = 0, device=None):
         if not float(epsilon) > 0.0:
             raise ValueError(f"epsilon must be positive, got {epsilon}")
+        if solver not in ("host", "device"):
+            raise ValueError(f'solver must be "host" or "device", got {solver!r}')
+        if solver == "device":
+            if n_eigenvectors is None:
+                raise ValueError('solver="device" needs n_eigenvectors, the number of diffusion coordinates to compute')
+            if not 1 <= int(n_eigenvectors) <= self.MAX_EIGENVECTORS:
+                raise ValueError(f'solver="device" computes 1..{self.MAX_EIGENVECTORS} diffusion coordinates, got '
+                                 f'n_eigenvectors = {n_eigenvectors}; use solver="host" for more')
+            if not np.isfinite(float(epsilon)):
+                raise ValueError(f"epsilon must be finite, got {epsilon}")
+            if int(max_iter) < 1:
+                raise ValueError(f"max_iter must be at least 1, got {max_iter}")
         self._dist = dist
         self.epsilon = float(epsilon)
+        self.n_eigenvectors = None if n_eigenvectors is None else int(n_eigenvectors)
+        self.solver = solver
+        self.tol, self.max_iter, self.seed = float(tol), int(max_iter), seed
+        self.device = device
         self.results = Results()
 
+    def _check_frames(self, n_frames: int) -> None:
+        """``block_width``'s refusal of k + 1 > F, in this class's terms."""
+        k = self.n_eigenvectors
+        try:
+            block_width(n_frames, k + 1)
+        except ValueError as e:
+            raise ValueError(f"n_eigenvectors = {k} diffusion coordinates and the constant mode are {k + 1} "
+                             f"eigenpairs, the matrix has {n_frames} frames: ask for at most "
+                             f"{min(n_frames, MAX_COMPONENTS) - 1}") from e
+
+    def _kernel_input_hbm(self, eng: Engine, start, stop, step, frames):
+        """(the distances as an f64 [F, F] HBM tensor this run may overwrite,
+        what its kernels read -- to be held until the stream has been waited
+        for)."""
+        d = self._dist
+        if isinstance(d, DistanceMatrix) and d.results.get("dist_matrix") is None:
+            d._refuse()
+
+            def check(n, dense):  # before anything is allocated or computed
+                self._check_frames(n)
+                check_pairwise_memory(eng, n, dense)
+
+            pairs = d._pairs_hbm(eng, start, stop, step, frames, check)
+            if pairs is None:
+                raise ValueError("the distance matrix has no frames")
+            args, work, keep = pairs
+            return d._store_matrix(eng, args, work), keep
+        if isinstance(d, DistanceMatrix):
+            d = d.results.dist_matrix
+        on_device = isinstance(d, torch.Tensor) and d.device.type == "cuda"
+        if on_device:
+            if d.dtype != torch.float64:
+                raise ValueError(f"an HBM distance matrix must be float64, got {d.dtype}")
+        else:
+            d = np.ascontiguousarray(d.cpu().numpy() if isinstance(d, torch.Tensor) else d, dtype=np.float64)
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise ValueError("the distance matrix must be square")
+        n = int(d.shape[0])
+        if n == 0:
+            raise ValueError("the distance matrix has no frames")
+        self._check_frames(n)
+        free = torch.cuda.mem_get_info(eng.device)[0]
+        if 8 * n * n > free // 2:
+            raise MemoryError(f"DiffusionMap: the copy of the [{n}, {n}] f64 matrix needs {8 * n * n} bytes, over "
+                              f"half of the {free} bytes of free HBM")
+        if on_device:
+            out = eng.empty(n, n)
+            out.copy_(d)
+            return out, None
+        return torch.as_tensor(d).to(eng.device), None
+
+    def _run_device(self, start, stop, step, frames):
+        k = self.n_eigenvectors + 1
+        eng = Engine(self.device)
+        with torch.cuda.device(eng.device):
+            kern, keep = self._kernel_input_hbm(eng, start, stop, step, frames)
+            n = int(kern.shape[0])
+            supplied = keep is None  # a matrix of the caller's, not one computed here
+            rowsum = eng.diffusion_kernel(kern, self.epsilon)
+            torch.cuda.current_stream(eng.device).synchronize()
+            del keep
+            rs = rowsum.cpu().numpy()
+            if not (np.all(np.isfinite(rs)) and np.all(rs > 0.0)):
+                bad = np.nonzero(~(np.isfinite(rs) & (rs > 0.0)))[0]
+                raise ValueError(f"the distance matrix has non-finite entries or rows whose kernel sums to zero: "
+                                 f"{bad.size} of the {n} row sums of exp(-d^2 / epsilon) are not positive and finite "
+                                 f"(the first is row {int(bad[0])})")
+            if supplied and not torch.equal(kern, kern.T):
+                raise ValueError('solver="device" needs a distance matrix that is exactly symmetric, d[i, j] == '
+                                 "d[j, i] (its product reads K[j, i] for K[i, j]); pass 0.5 * (d + d.T), or use "
+                                 'solver="host", which symmetrises the conjugate matrix itself')
+            t = 1.0 / np.sqrt(rs)
+            ops = KernelOps(kern, torch.as_tensor(t).to(eng.device), engine=eng)
+            w, v, info = top_eigenpairs(None, k, tol=self.tol, max_iter=self.max_iter, seed=self.seed, ops=ops)
+        right = v * t[:, None]
+        if right[:, 0].sum() < 0:  # the constant vector, positive
+            right[:, 0] = -right[:, 0]
+        self.results.eigenvalues = w
+        self.results.eigenvectors = np.ascontiguousarray(right)
+        self.results.n_frames = n
+        self.results.solver_info = info
+        return self
+
     def run(self, start=None, stop=None, step=None, frames=None):
+        if self.solver == "device":
+            return self._run_device(start, stop, step, frames)
         d = self._dist
         if isinstance(d, DistanceMatrix):
             if d.results.get("dist_matrix") is None:
@@ -596,5 +746,6 @@ class DiffusionMap:
         w, v = self.results.eigenvalues, self.results.eigenvectors
         n = int(n_eigenvectors)
         if not 1 <= n <= len(w) - 1:
-            raise ValueError(f"n_eigenvectors must be in 1..{len(w) - 1}, got {n_eigenvectors}")
+            raise ValueError(f"n_eigenvectors must be in 1..{len(w) - 1}, the diffusion coordinates this run computed, "
+                             f"got {n_eigenvectors}")
         return v[:, 1:n + 1] * (w[1:n + 1] ** time)

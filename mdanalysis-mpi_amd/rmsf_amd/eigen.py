@@ -12,7 +12,10 @@ matrix cores, the matrix and every block in HBM) and over ``NumpyOps`` (the
 whole iteration, its stopping rule and its breakdown paths on the CPU).
 ``TrajectoryOps`` overrides ``symm`` alone: M Q = D^T (D Q) / denom from the
 trajectory's frames (csrc/pca_project.hip and csrc/pca_backproject.hip), so no
-n x n matrix exists at all; ``FactorOps`` is its numpy twin.  The
+n x n matrix exists at all; ``FactorOps`` is its numpy twin.  ``KernelOps``
+does the same for M = diag(t) K diag(t) with K in HBM (csrc/diffusion.hip's
+row scaling around ``DeviceOps``' product; ``DiffusionMap(solver="device")``),
+and ``ScaledOps`` is its numpy twin.  The
 b x b steps -- ``numpy.linalg.eigh`` of a Gram matrix or of the projected
 matrix -- run on the host: a few stream synchronisations per iteration.
 
@@ -161,6 +164,51 @@ class FactorOps(NumpyOps):
 
     def symm(self, q):
         return self.d.T @ (self.d @ q) / self.denom
+
+
+class ScaledOps(NumpyOps):
+    """The numpy twin of ``KernelOps``: the matrix diag(t) K diag(t) through
+    K and t alone, ``symm(q) = t * (K @ (t * q))``.  The scaled matrix is
+    never formed."""
+
+    def __init__(self, matrix, t):
+        super().__init__(matrix)
+        t = np.asarray(t, dtype=np.float64).reshape(-1)
+        if t.size != self.n:
+            raise ValueError(f"t must have {self.n} entries, got {t.size}")
+        self.t = t
+
+    def symm(self, q):
+        return self.t[:, None] * (self.m @ (self.t[:, None] * q))
+
+
+class KernelOps(DeviceOps):
+    """A diagonally scaled matrix as an operator:
+
+        symm(Q) = diag(t) K (diag(t) Q)
+
+    with K [n, n] (symmetric in its bits) and t [n], both f64 in HBM: one
+    ``block_scale_rows``, ``DeviceOps``' product with K, a second
+    ``block_scale_rows`` in place.  diag(t) K diag(t) is never written.
+    With K a diffusion kernel and t = rowsum^-1/2 that is the symmetric
+    conjugate of the transition matrix (``DiffusionMap(solver="device")``).
+    ``put``, ``get``, ``gram`` and ``update`` are ``DeviceOps``' own."""
+
+    def __init__(self, matrix, t, engine=None):
+        import torch
+        super().__init__(matrix, engine)
+        if not isinstance(t, torch.Tensor) or t.device != matrix.device or t.dtype != torch.float64 \
+                or t.dim() != 1 or t.shape[0] != self.n or not t.is_contiguous():
+            raise ValueError(f"t must be a contiguous f64 HIP tensor [{self.n}] on the matrix's device")
+        self.t = t
+
+    def symm(self, q):
+        b = int(q.shape[1])
+        tq = self.eng.empty(self.n, b)
+        self.eng.block_scale_rows(self.t, q, self.n, b, tq)
+        y = super().symm(tq)
+        self.eng.block_scale_rows(self.t, y, self.n, b, y)
+        return y
 
 
 _TRAJ_ONE_DEVICE = "the matrix-free product runs on one device per process: not "

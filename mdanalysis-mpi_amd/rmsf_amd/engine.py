@@ -506,6 +506,28 @@ class Engine:
         call("rmsf_block_update", float(alpha), _ptr(a), 0 if a is None else a.stride(0), b.data_ptr(), b.stride(0),
              nb, t.data_ptr(), t.stride(0), n, nc, c.data_ptr(), c.stride(0), self.stream)
 
+    # -- diffusion kernel of a distance matrix (csrc/diffusion.hip) -------------
+    def diffusion_kernel(self, m: torch.Tensor, epsilon: float, n: int | None = None) -> torch.Tensor:
+        """``m[:n, :n]`` (f64 distances in HBM) becomes ``exp(-(m * m) /
+        epsilon)`` in place; returns the f64 [n] sums of its rows
+        (rmsf_diffusion_kernel).  Columns past ``n`` are neither read nor
+        written."""
+        n = m.shape[0] if n is None else n
+        if m.dtype != F64 or m.dim() != 2 or m.stride(1) != 1 or m.shape[0] < n or m.shape[1] < n or n < 1:
+            raise ValueError("diffusion_kernel: buffer sizes")
+        rowsum = self.empty(n)
+        call("rmsf_diffusion_kernel", m.data_ptr(), m.stride(0), n, float(epsilon), rowsum.data_ptr(), self.stream)
+        return rowsum
+
+    def block_scale_rows(self, s: torch.Tensor, a: torch.Tensor, n: int, nc: int, c: torch.Tensor) -> None:
+        """c[:n, :nc] = s[:n, None] * a[:n, :nc] (rmsf_block_scale_rows).
+        ``c`` may be ``a``."""
+        if not (self._is_block(a, n, nc) and self._is_block(c, n, nc) and s.dtype == F64 and s.numel() >= n
+                and s.is_contiguous()):
+            raise ValueError("block_scale_rows: buffer sizes")
+        call("rmsf_block_scale_rows", s.data_ptr(), a.data_ptr(), a.stride(0), n, nc, c.data_ptr(), c.stride(0),
+             self.stream)
+
     # -- all-pairs RMSD matrix (csrc/pairwise.hip) ----------------------------
     def pairwise_centres(self, xyz_ptr: int, fstride: int, n_frames: int, n_sel: int, sel, weights,
                          per_frame: bool = True):

@@ -68,6 +68,15 @@ def main(argv=None) -> int:
                          "'bits' has the pair kernel write the bits and stores no matrix (F^2 / 8 bytes: what fits "
                          "at 10^5 - 10^6 frames); 'auto' (the default) takes 'f64' where it fits and 'bits' where "
                          "it does not")
+    ap.add_argument("--diffusion-map", default=None, metavar="OUT.npy",
+                    help="also write the diffusion-map embedding of the frames at time 1, f64 [F, K]: the first K "
+                         "diffusion coordinates of the RMSD matrix --dist-matrix writes, which stays in HBM "
+                         '(rmsf_amd.DiffusionMap, solver="device"; needs --diffusion-epsilon and --n-eigenvectors; '
+                         "one process only)")
+    ap.add_argument("--diffusion-epsilon", type=float, default=None, metavar="E",
+                    help="--diffusion-map: the kernel's scale in A^2, K = exp(-d^2 / E)")
+    ap.add_argument("--n-eigenvectors", type=int, default=None, metavar="K",
+                    help="--diffusion-map: the number of diffusion coordinates, 1..39")
     ap.add_argument("--cross-rmsd", default=None, metavar="OUT.npy",
                     help="also write the RMSD of every frame of the trajectory to every frame of --cross-with, "
                          "f64 [F, F_b] (rmsf_amd.CrossDistanceMatrix; each pair superposed unless --align none; "
@@ -103,6 +112,13 @@ def main(argv=None) -> int:
         ap.error("--cluster-cutoff must be >= 0")
     if a.cluster and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--cluster runs in one process (no torch.distributed launch)")
+    if bool(a.diffusion_map) != (a.diffusion_epsilon is not None) or bool(a.diffusion_map) != (
+            a.n_eigenvectors is not None):
+        ap.error("--diffusion-map OUT.npy, --diffusion-epsilon E and --n-eigenvectors K go together")
+    if a.diffusion_map and not (a.diffusion_epsilon > 0.0 and 1 <= a.n_eigenvectors <= 39):
+        ap.error("--diffusion-epsilon must be > 0 and --n-eigenvectors in 1..39")
+    if a.diffusion_map and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--diffusion-map runs in one process (no torch.distributed launch)")
     if bool(a.cross_rmsd) != bool(a.cross_with):
         ap.error("--cross-rmsd OUT.npy and --cross-with TRAJ go together")
     if a.cross_rmsd and a.synthetic:
@@ -203,6 +219,15 @@ def main(argv=None) -> int:
               f"{'the stored f64 matrix' if cl.matrix_form == 'f64' else 'the pair kernel, no matrix stored'})",
               flush=True)
         np.save(a.cluster, cl.labels)
+    if a.diffusion_map:
+        from rmsf_amd import DiffusionMap, DistanceMatrix
+        dmap = DiffusionMap(DistanceMatrix(dm_input, superposition=align is not None, **dm_kw),
+                            epsilon=a.diffusion_epsilon, n_eigenvectors=a.n_eigenvectors, solver="device").run()
+        emb = dmap.transform(a.n_eigenvectors, 1.0)
+        print(f"diffusion map of {emb.shape[0]} frames at epsilon {a.diffusion_epsilon} A^2: eigenvalues "
+              f"{np.array2string(dmap.results.eigenvalues[1:], precision=6)} after the constant mode, "
+              f"{dmap.results.solver_info['n_iter']} iterations", flush=True)
+        np.save(a.diffusion_map, emb)
     if a.cross_rmsd:
         from rmsf_amd import CrossDistanceMatrix
         cm = CrossDistanceMatrix(dm_input, cross_b, superposition=align is not None, **dm_kw).run().results
