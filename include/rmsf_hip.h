@@ -861,6 +861,55 @@ int rmsf_pairwise_adjacency(const float *d_xyz, int64_t frame_stride,
                             int64_t ldw, int32_t *d_count, void *d_work,
                             size_t work_bytes, void *stream);
 
+/* ---- DBSCAN on the neighbour bits (Ester et al. 1996) -----------------------
+ * scikit-learn's definition (sklearn.cluster.DBSCAN, metric="precomputed"),
+ * restated so that it needs no visiting order; the same for the device entry,
+ * rmsf_cluster_dbscan_host and the tests' numpy reference:
+ *   adj and count are those of the GROMOS section above (diagonal set, a NaN
+ *   never a neighbour).  core[i] = (count[i] >= min_samples).  The clusters are
+ *   the connected components of adj restricted to core x core; a cluster's id
+ *   is the rank of its lowest core index among all clusters' lowest core
+ *   indices.  A non-core row with at least one core neighbour is a border row
+ *   and takes the lowest cluster id among its core neighbours' clusters (not
+ *   the cluster of its lowest-indexed core neighbour).  Every other row is
+ *   noise, -1.  min_samples = 1 is single linkage at the cutoff.  Integers
+ *   only: the same result on every run.
+ * rmsf_cluster_dbscan: on d_adj[n][ldw] (symmetric) and d_count[n], both read
+ *   and not changed.  d_label[n] (int32) receives the labels, d_core
+ *   [rmsf_adjacency_words(n)] (uint64) the core bits (bits >= n are 0), and the
+ *   host words *h_n_clusters and *h_n_rounds the number of clusters and of
+ *   rounds.  The components are found by min-hooking with shortcutting (the
+ *   FastSV family): a parent array f starts as the identity; a round gives
+ *   every core row the minimum grandparent f[f[j]] over its core neighbours j,
+ *   hooks it onto the row's parent and onto the row (integer atomicMin into
+ *   the next round's array: the minimum of a set, whatever the order) and so
+ *   shortcuts f[i] to f[f[i]]; each round reads the core rows once, n^2 / 8
+ *   bytes at the most.  Two launches a round, enqueued 4 rounds at a time;
+ *   after each batch the call reads one state word back, and it stops after
+ *   the first round that changes nothing: *h_n_rounds counts that round too.
+ *   More than n + 1 rounds is RMSF_EHIP and no labels (a guard only: after t
+ *   rounds f[i] is at most what plain min-propagation has after t, and that
+ *   settles within the graph's diameter, below n).
+ *   Then the roots' ranks (one workgroup's popcount scan) and the labels, one
+ *   wavefront a row.  The stream is idle when the call returns.  d_work:
+ *   rmsf_cluster_dbscan_workspace_bytes(n) bytes, a function of n alone, O(n)
+ *   (0 for n outside 1..INT32_MAX); NULL or too small is RMSF_ENOMEM.
+ * rmsf_cluster_dbscan_host: the same definition in plain C++ on a host matrix
+ *   h_m[n][ld] thresholded at cutoff (>= 0; a NaN is refused); touches no
+ *   device; h_label[n], h_core[rmsf_adjacency_words(n)] and *h_n_clusters are
+ *   host pointers.
+ * n in 1..INT32_MAX, min_samples >= 1; every check comes before any launch.  */
+size_t rmsf_cluster_dbscan_workspace_bytes(int64_t n);
+int rmsf_cluster_dbscan(const uint64_t *d_adj, int64_t n, int64_t ldw,
+                        const int32_t *d_count, int64_t min_samples,
+                        int32_t *d_label, uint64_t *d_core,
+                        int32_t *h_n_clusters, int32_t *h_n_rounds,
+                        void *d_work, size_t work_bytes, void *stream);
+int rmsf_cluster_dbscan_host(const double *h_m, int64_t n, int64_t ld,
+                             double cutoff, int64_t min_samples,
+                             int32_t *h_label, uint64_t *h_core,
+                             int32_t *h_n_clusters);
+
 /* ---- qcprot.CalcRMSDRotationalMatrix (RMSF.py:48) --------------------------
  * Batched QCP on device: A[n][9], E0[n], atom counts N[n] -> rot[n][9],
  * rmsd[n].  Exposed for the upstream known-answer test.                      */

@@ -24,6 +24,10 @@ Public surface (mirrors the reference's names):
   * ``Cluster`` -- GROMOS clustering (Daura et al. 1999) of the frames from their RMSD matrix,
     which is thresholded into neighbour bits and clustered in HBM without crossing to the host:
     ``Cluster(traj, cutoff=1.5).run().results.labels`` / ``.centres`` / ``.sizes``
+  * ``DBSCAN`` -- density clustering of the same neighbour bits, named as sklearn.cluster.DBSCAN
+    names it and equal to it with ``metric="precomputed"``: core frames, their connected components,
+    border frames and noise (-1), all in HBM:
+    ``DBSCAN(traj, eps=1.5, min_samples=5).run().results.labels`` / ``.core_sample_indices``
 """
 from ._lib import RmsfEmptyError, RmsfError, load as load_library
 from .parallel import blocks
@@ -33,7 +37,7 @@ from .rms import RMSF, Results
 from .eigen import PCAConvergenceError
 from .pca import PCA, cosine_content, cumulative_overlap, pca_from_comoment, rmsip
 from .distances import CrossDistanceMatrix, DiffusionMap, DistanceMatrix, discrete_frechet, hausdorff
-from .clustering import Cluster
+from .clustering import DBSCAN, Cluster
 
 __all__ = [
     "RMSF",
@@ -50,6 +54,7 @@ __all__ = [
     "hausdorff",
     "discrete_frechet",
     "Cluster",
+    "DBSCAN",
     "blocks",
     "second_order_moments",
     "get_rotation_matrix",

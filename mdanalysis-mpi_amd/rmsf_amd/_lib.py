@@ -136,6 +136,9 @@ SIGNATURES = {
     "rmsf_adjacency_count": (c_int, [P, c_int64, c_int64, P, P]),
     "rmsf_pairwise_adjacency": (c_int, [P, c_int64, c_int64, c_int64, P, P, c_double, P, P, c_int, c_double, c_double,
                                         P, c_int64, P, P, c_size_t, P]),
+    "rmsf_cluster_dbscan_workspace_bytes": (c_size_t, [c_int64]),
+    "rmsf_cluster_dbscan": (c_int, [P, c_int64, c_int64, P, c_int64, P, P, P, P, P, c_size_t, P]),
+    "rmsf_cluster_dbscan_host": (c_int, [P, c_int64, c_int64, c_double, c_int64, P, P, P]),
     "rmsf_qcp_batch": (c_int, [P, P, P, c_int64, P, P, P]),
     "rmsf_calc_rmsd_rotational_matrix": (c_int, [P, P, c_int64, P, P, POINTER(c_double)]),
     "rmsf_synth_frames": (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_uint64, P, P]),

@@ -682,6 +682,28 @@ class Engine:
              centre.data_ptr(), size.data_ptr(), ctypes.byref(k), work.data_ptr(), need, self.stream)
         return label, centre[:k.value], size[:k.value]
 
+    def cluster_dbscan(self, adj: torch.Tensor, count: torch.Tensor, min_samples: int):
+        """(labels int32 [n], core bits as int64 [adjacency_words(n)],
+        n_clusters, n_rounds): DBSCAN on adjacency_pack's bits and counts
+        (rmsf_cluster_dbscan, csrc/dbscan.hip; ``adj`` and ``count`` are left
+        as they are).  -1 is noise.  Returns after the last read of its state:
+        the stream is idle."""
+        n = adj.shape[0]
+        if (adj.dtype != torch.int64 or adj.dim() != 2 or adj.stride(1) != 1 or count.dtype != torch.int32
+                or count.numel() < n or not count.is_contiguous() or adj.shape[1] < self.adjacency_words(n) or n < 1):
+            raise ValueError("cluster_dbscan: buffer sizes")
+        if int(min_samples) != min_samples or min_samples < 1:
+            raise ValueError(f"cluster_dbscan: min_samples must be an integer >= 1, got {min_samples!r}")
+        label = torch.empty(n, dtype=torch.int32, device=self.device)
+        core = torch.empty(self.adjacency_words(n), dtype=torch.int64, device=self.device)
+        need = int(self.lib.rmsf_cluster_dbscan_workspace_bytes(n))
+        work = torch.empty(need // 8, dtype=torch.int64, device=self.device)
+        k, rounds = ctypes.c_int32(0), ctypes.c_int32(0)
+        call("rmsf_cluster_dbscan", adj.data_ptr(), n, adj.stride(0), count.data_ptr(),
+             min(int(min_samples), 2 ** 62), label.data_ptr(), core.data_ptr(), ctypes.byref(k), ctypes.byref(rounds),
+             work.data_ptr(), need, self.stream)
+        return label, core, k.value, rounds.value
+
     def qcp_batch(self, A: torch.Tensor, E0: torch.Tensor, N: torch.Tensor):
         n = A.shape[0]
         rot = self.empty(n, 9)

@@ -64,10 +64,19 @@ def main(argv=None) -> int:
     ap.add_argument("--cluster-cutoff", type=float, default=None, metavar="C",
                     help="--cluster: the cluster radius in A, frames within C of each other are neighbours")
     ap.add_argument("--cluster-matrix", choices=["auto", "f64", "bits"], default=None,
-                    help="--cluster: 'f64' stores the F x F RMSD matrix in HBM and packs it into neighbour bits; "
+                    help="--cluster / --dbscan: 'f64' stores the F x F RMSD matrix in HBM and packs it into neighbour bits; "
                          "'bits' has the pair kernel write the bits and stores no matrix (F^2 / 8 bytes: what fits "
                          "at 10^5 - 10^6 frames); 'auto' (the default) takes 'f64' where it fits and 'bits' where "
                          "it does not")
+    ap.add_argument("--dbscan", default=None, metavar="OUT.npy",
+                    help="also write the DBSCAN cluster of every frame, int64 [F], -1 for noise, clusters numbered by "
+                         "their first core frame (rmsf_amd.DBSCAN on the RMSD matrix --dist-matrix writes, which stays "
+                         "in HBM; needs --dbscan-eps; --cluster-matrix applies; one process only)")
+    ap.add_argument("--dbscan-eps", type=float, default=None, metavar="E",
+                    help="--dbscan: the neighbourhood radius in A, frames within E of each other are neighbours")
+    ap.add_argument("--dbscan-min-samples", type=int, default=None, metavar="M",
+                    help="--dbscan: a frame with at least M frames within E, itself included, is a core frame "
+                         "(default 5; 1 is single linkage)")
     ap.add_argument("--diffusion-map", default=None, metavar="OUT.npy",
                     help="also write the diffusion-map embedding of the frames at time 1, f64 [F, K]: the first K "
                          "diffusion coordinates of the RMSD matrix --dist-matrix writes, which stays in HBM "
@@ -106,12 +115,22 @@ def main(argv=None) -> int:
         ap.error("--dist-matrix runs in one process (no torch.distributed launch)")
     if bool(a.cluster) != (a.cluster_cutoff is not None):
         ap.error("--cluster OUT.npy and --cluster-cutoff C go together")
-    if a.cluster_matrix and not a.cluster:
-        ap.error(f"--cluster-matrix {a.cluster_matrix} needs --cluster")
+    if a.cluster_matrix and not (a.cluster or a.dbscan):
+        ap.error(f"--cluster-matrix {a.cluster_matrix} needs --cluster or --dbscan")
     if a.cluster and not a.cluster_cutoff >= 0.0:
         ap.error("--cluster-cutoff must be >= 0")
     if a.cluster and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--cluster runs in one process (no torch.distributed launch)")
+    if bool(a.dbscan) != (a.dbscan_eps is not None):
+        ap.error("--dbscan OUT.npy and --dbscan-eps E go together")
+    if a.dbscan_min_samples is not None and not a.dbscan:
+        ap.error("--dbscan-min-samples needs --dbscan")
+    if a.dbscan and not a.dbscan_eps >= 0.0:
+        ap.error("--dbscan-eps must be >= 0")
+    if a.dbscan and a.dbscan_min_samples is not None and a.dbscan_min_samples < 1:
+        ap.error("--dbscan-min-samples must be >= 1")
+    if a.dbscan and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--dbscan runs in one process (no torch.distributed launch)")
     if bool(a.diffusion_map) != (a.diffusion_epsilon is not None) or bool(a.diffusion_map) != (
             a.n_eigenvectors is not None):
         ap.error("--diffusion-map OUT.npy, --diffusion-epsilon E and --n-eigenvectors K go together")
@@ -219,6 +238,15 @@ def main(argv=None) -> int:
               f"{'the stored f64 matrix' if cl.matrix_form == 'f64' else 'the pair kernel, no matrix stored'})",
               flush=True)
         np.save(a.cluster, cl.labels)
+    if a.dbscan:
+        from rmsf_amd import DBSCAN
+        db = DBSCAN(dm_input, eps=a.dbscan_eps, min_samples=5 if a.dbscan_min_samples is None else a.dbscan_min_samples,
+                    superposition=align is not None, matrix=a.cluster_matrix or "auto", **dm_kw).run().results
+        print(f"DBSCAN clusters at {a.dbscan_eps} A, {db.n_rounds} rounds, over {db.n_frames} frames: {db.n_clusters}, "
+              f"{len(db.core_sample_indices)} core frames, {db.n_noise} noise (neighbour bits from "
+              f"{'the stored f64 matrix' if db.matrix_form == 'f64' else 'the pair kernel, no matrix stored'})",
+              flush=True)
+        np.save(a.dbscan, db.labels)
     if a.diffusion_map:
         from rmsf_amd import DiffusionMap, DistanceMatrix
         dmap = DiffusionMap(DistanceMatrix(dm_input, superposition=align is not None, **dm_kw),
