@@ -537,6 +537,45 @@ int rmsf_covariance_accumulate(const float *d_xyz, int64_t frame_stride,
 int rmsf_covariance_finish(double *d_cov, int64_t ld, const double *d_t1,
                            int64_t n_coord, int64_t n_frames, void *stream);
 
+/* ---- time-lagged co-moment (the contraction of TICA) -----------------------
+ * The covariance contraction with its two operands apart in time, on the f64
+ * matrix cores (csrc/lagged.hip).  Coordinate index i = 3 a + c over the
+ * selection's order, p and d as rmsf_covariance_accumulate has them.  Pair q
+ * of the batch is frame q of operand A (d_xyz_a, frame_stride_a, records
+ * d_xform_a) and frame q of operand B (d_xyz_b, frame_stride_b, d_xform_b);
+ * for one resident array the caller passes b = a + lag * stride (and its
+ * records lag further on): the kernel never adds a lag itself.
+ * rmsf_lagged_comoment_accumulate:
+ *   d_s[i * ld + j] += sum_q d_i(frame q of A) d_j(frame q of B)
+ * for every i, j < 3 n_sel: all of the matrix, which is not symmetric.  The
+ * caller zeroes d_s (ld >= 3 n_sel doubles a row) before the first batch.
+ * Work is cut into (48 x 48 tile, pair range) workgroups over the full square
+ * of tiles; with more than one pair range the partials go to d_work
+ * (rmsf_lagged_comoment_workspace_bytes() bytes, host-only arithmetic, 0 when
+ * none is needed and d_work may be NULL) and are summed in range order by a
+ * second launch: no floating-point atomics, the same bits for the same
+ * inputs and batching.  d_xform_a, d_xform_b and d_refinfo are given
+ * together or all NULL (RMSF_EINVAL otherwise, as for a NULL pointer or
+ * ld < 3 n_sel; a workspace too small: RMSF_ENOMEM); n_pairs == 0: RMSF_OK.
+ * rmsf_lagged_comoment_finish, after the last batch, with d_t[i] = the sum of
+ * d_i over both windows' frames (m of them in all):
+ *   d_s = d_s + d_s^T - d_t d_t^T / m  in place, each element's sum formed
+ *   once and stored to (i, j) and (j, i): exactly symmetric.                */
+size_t rmsf_lagged_comoment_workspace_bytes(int64_t n_sel, int64_t n_pairs);
+int rmsf_lagged_comoment_accumulate(const float *d_xyz_a,
+                                    int64_t frame_stride_a,
+                                    const float *d_xyz_b,
+                                    int64_t frame_stride_b, int64_t n_pairs,
+                                    int64_t n_sel, const int32_t *d_sel,
+                                    const double *d_xform_a,
+                                    const double *d_xform_b,
+                                    const double *d_refinfo,
+                                    const double *d_shift, double *d_s,
+                                    int64_t ld, void *d_work,
+                                    size_t work_bytes, void *stream);
+int rmsf_lagged_comoment_finish(double *d_s, int64_t ld, const double *d_t,
+                                int64_t n_coord, int64_t m, void *stream);
+
 /* ---- PCA projection (MDAnalysis.analysis.pca.PCA.transform) ----------------
  * The projection of a batch's frames on n_comp components, a tall, skinny
  * product [n_frames x 3 n_sel] . [3 n_sel x n_comp] on the f64 matrix cores

@@ -28,6 +28,10 @@ Public surface (mirrors the reference's names):
     names it and equal to it with ``metric="precomputed"``: core frames, their connected components,
     border frames and noise (-1), all in HBM:
     ``DBSCAN(traj, eps=1.5, min_samples=5).run().results.labels`` / ``.core_sample_indices``
+  * ``TICA`` / ``tica_from_comoments`` -- the slowest modes of the trajectory from the covariance and the
+    time-lagged covariance of the (aligned) coordinates, the latter on the f64 matrix cores with its two
+    operands ``lag`` frames apart: ``TICA(traj, lag=10).run().results.timescales`` / ``.components``;
+    ``TICA.transform`` projects on them as ``PCA.transform`` does
 """
 from ._lib import RmsfEmptyError, RmsfError, load as load_library
 from .parallel import blocks
@@ -38,8 +42,11 @@ from .eigen import PCAConvergenceError
 from .pca import PCA, cosine_content, cumulative_overlap, pca_from_comoment, rmsip
 from .distances import CrossDistanceMatrix, DiffusionMap, DistanceMatrix, discrete_frechet, hausdorff
 from .clustering import DBSCAN, Cluster
+from .tica import TICA, tica_from_comoments
 
 __all__ = [
+    "TICA",
+    "tica_from_comoments",
     "RMSF",
     "Results",
     "PCA",

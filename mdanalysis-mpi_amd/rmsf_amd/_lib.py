@@ -104,6 +104,10 @@ SIGNATURES = {
     "rmsf_covariance_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "rmsf_covariance_accumulate": (c_int, [P, c_int64, c_int64, c_int64, P, P, P, P, P, c_int64, P, P, c_size_t, P]),
     "rmsf_covariance_finish": (c_int, [P, c_int64, P, c_int64, c_int64, P]),
+    "rmsf_lagged_comoment_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rmsf_lagged_comoment_accumulate": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P, P, P, P, P, P, c_int64, P,
+                                                c_size_t, P]),
+    "rmsf_lagged_comoment_finish": (c_int, [P, c_int64, P, c_int64, c_int64, P]),
     "rmsf_pca_project_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "rmsf_pca_project": (c_int, [P, c_int64, c_int64, c_int64, P, P, P, P, P, c_int64, c_int64, P, c_int64, P, c_size_t,
                                  P]),

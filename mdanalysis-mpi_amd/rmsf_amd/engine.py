@@ -411,6 +411,36 @@ class Engine:
             raise ValueError("covariance_finish: buffer sizes")
         call("rmsf_covariance_finish", cov.data_ptr(), cov.stride(0), t1.data_ptr(), n_coord, n_frames, self.stream)
 
+    # -- time-lagged co-moment (csrc/lagged.hip) -------------------------------
+    def lagged_comoment_workspace_bytes(self, n_sel: int, n_pairs: int) -> int:
+        return int(self.lib.rmsf_lagged_comoment_workspace_bytes(n_sel, n_pairs))
+
+    def lagged_comoment_accumulate(self, xyz_a_ptr: int, fstride_a: int, xyz_b_ptr: int, fstride_b: int,
+                                   n_pairs: int, n_sel: int, sel, xform_a, xform_b, refinfo, shift: torch.Tensor,
+                                   s: torch.Tensor, work: torch.Tensor | None = None) -> None:
+        """s[i, j] += sum_q d_i(frame q of A) d_j(frame q of B) over the
+        batch's pairs, all of the matrix, d = f64(p) - shift as in
+        ``covariance_accumulate`` -- each operand through its own transform
+        records when ``xform_a``, ``xform_b`` and ``refinfo`` are given -- on
+        the f64 matrix cores (rmsf_lagged_comoment_accumulate).  The caller
+        offsets B by the lag.  ``work``: f64 scratch of at least
+        lagged_comoment_workspace_bytes(n_sel, n_pairs) bytes (None when 0)."""
+        n = 3 * n_sel
+        if (s.dtype != F64 or shift.dtype != F64 or s.dim() != 2 or s.stride(1) != 1 or s.shape[0] < n
+                or s.shape[1] < n or shift.numel() < n):
+            raise ValueError("lagged_comoment_accumulate: buffer sizes")
+        call("rmsf_lagged_comoment_accumulate", xyz_a_ptr, fstride_a, xyz_b_ptr, fstride_b, n_pairs, n_sel, _ptr(sel),
+             _ptr(xform_a), _ptr(xform_b), _ptr(refinfo), shift.data_ptr(), s.data_ptr(), s.stride(0), _ptr(work),
+             0 if work is None else work.numel() * work.element_size(), self.stream)
+
+    def lagged_comoment_finish(self, s: torch.Tensor, t: torch.Tensor, n_coord: int, m: int) -> None:
+        """s = s + s^T - t t^T / m in place, symmetric in its bits
+        (rmsf_lagged_comoment_finish)."""
+        if (s.dtype != F64 or t.dtype != F64 or s.dim() != 2 or s.stride(1) != 1 or s.shape[0] < n_coord
+                or s.shape[1] < n_coord or t.numel() < n_coord):
+            raise ValueError("lagged_comoment_finish: buffer sizes")
+        call("rmsf_lagged_comoment_finish", s.data_ptr(), s.stride(0), t.data_ptr(), n_coord, m, self.stream)
+
     # -- PCA projection (csrc/pca_project.hip) ---------------------------------
     def pca_project_workspace_bytes(self, n_frames: int, n_sel: int, n_comp: int) -> int:
         return int(self.lib.rmsf_pca_project_workspace_bytes(n_frames, n_sel, n_comp))

@@ -176,6 +176,126 @@ def check_projection_memory(eng, n_frames: int, n_comp: int) -> None:
                           f"of the {free} bytes of free HBM")
 
 
+def refuse_one_device(rmsf, atomgroup, what: str = "PCA.transform") -> None:
+    """What reads the trajectory of ``rmsf`` (an ``RMSF``) or ``atomgroup`` on
+    one device per process -- ``PCA.transform``, ``PCA(solver="matrix_free")``,
+    ``TICA`` (``what``) -- refuses, before any launch."""
+    import torch
+
+    from . import parallel
+    from .sources import DeviceSource
+
+    one_device = _ONE_DEVICE.replace("PCA.transform", what)
+    r = rmsf
+    for x in (r._input, atomgroup):
+        if isinstance(x, (list, tuple)):
+            raise NotImplementedError(one_device + "with gpus= or a list of shards")
+    if r.gpus is not None:
+        raise NotImplementedError(one_device + "with gpus= or a list of shards")
+    x = r._input if atomgroup is None else atomgroup
+    if (isinstance(x, DeviceSource) and x.layout == "soa") or (
+            isinstance(x, torch.Tensor) and x.device.type == "cuda" and r.layout == "soa"):
+        raise NotImplementedError(_PLANES.replace("PCA.transform", what))
+    if parallel.world()[1] > 1:
+        raise NotImplementedError(one_device + "under torch.distributed with more than one rank")
+
+
+def project_on_components(rmsf, comps, mean, what: str, atomgroup=None, n_components: int | None = None,
+                          start=None, stop=None, step=None, frames=None, as_tensor: bool = False):
+    """``PCA.transform``'s path, for any [3n, k] set of columns ``comps`` and
+    any ``mean`` [n, 3] over the selection of ``rmsf`` (the ``RMSF`` whose run
+    supplied the superposition): see ``PCA.transform``.  ``what`` names the
+    caller in the messages."""
+    if comps is None:
+        raise ValueError(f"{what} needs the components: call run() first (the non-root ranks of a "
+                         "reduce-to-root merge hold none)")
+    k_total = int(comps.shape[1])
+    k = k_total if n_components is None else int(n_components)
+    if not 1 <= k <= k_total:
+        raise ValueError(f"n_components must be in 1..{k_total}, got {n_components}")
+    refuse_one_device(rmsf, atomgroup, what)
+    r = rmsf
+    last = r._last_run
+    if last is None:
+        # results filled in by hand (components kept from an earlier run): without alignment there is
+        # no superposition to repeat, and the PCA's own input can be projected
+        if r.align is not None:
+            raise ValueError(f"{what} needs the superposition of run(): these results were not computed "
+                             "by run() on this object")
+        last = {"source": None, "frames": None, "masses": None, "device": r.device, "exact": False,
+                "ref": None, "refinfo": None}
+
+    import torch
+
+    from ._lib import RMSF_XFORM_DOUBLES
+    from .engine import Engine
+    from .pipeline import Superposer
+    from .rms import make_source
+    from .sources import DeviceSource, FrameList
+
+    eng = Engine(last["device"])
+    with torch.cuda.device(eng.device):
+        if atomgroup is None and last["source"] is None:
+            atomgroup = r._input
+        if atomgroup is None:
+            src = last["source"]
+            same = start is None and stop is None and step is None and frames is None
+            fl = last["frames"] if same else FrameList(src.n_traj, start, stop, step, frames=frames)
+        else:
+            src, _ = make_source(atomgroup, select=r.select, masses=r.masses, align=None,
+                                 batch_frames=r.batch_frames, layout=r.layout, group_masses=False)
+            fl = FrameList(src.n_traj, start, stop, step, frames=frames)
+        if isinstance(src, DeviceSource) and src.layout == "soa":
+            raise NotImplementedError(_PLANES.replace("PCA.transform", what))
+        n_sel = src.n_sel
+        if 3 * n_sel != comps.shape[0]:
+            raise ValueError(f"the input selects {n_sel} atoms, the components were computed for "
+                             f"{comps.shape[0] // 3}")
+        n_frames = len(fl)
+        check_projection_memory(eng, n_frames, k)
+        out = eng.empty(n_frames, k)
+        if n_frames == 0:
+            return out if as_tensor else out.cpu().numpy()
+        mean = torch.as_tensor(np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)).to(eng.device)
+        comp = torch.as_tensor(np.ascontiguousarray(comps, dtype=np.float64)).to(eng.device)
+        max_batch = max(1, min(r.batch_frames or n_frames, n_frames))
+        aligned = r.align is not None
+        exact = bool(last["exact"])
+        ref, info = last["ref"], last["refinfo"]
+        m_dev, mass_total, sup, xf = None, float(n_sel), None, None
+        if aligned:
+            masses = last["masses"]
+            if masses is not None:
+                m_np = np.ascontiguousarray(masses, dtype=np.float64)
+                mass_total = float(m_np.sum())  # numpy's own sum, as the exact run's (pipeline._run_exact)
+                m_dev = torch.as_tensor(m_np).to(eng.device)
+            if exact:
+                xf = eng.empty(max_batch, RMSF_XFORM_DOUBLES)
+            else:
+                sup = Superposer(eng, n_sel, max_batch, m_dev)
+        work, done = None, 0
+        for b in src.batches(fl, 0, n_frames, max_batch, eng.stream):
+            if b.pstride:
+                raise NotImplementedError(_PLANES.replace("PCA.transform", what))
+            x = None
+            if aligned and exact:
+                x = xf[:b.n_frames]
+                eng.superpose_seq(b.ptr, b.fstride, b.n_frames, n_sel, b.sel, m_dev, mass_total, ref, info, x)
+            elif aligned:
+                x = sup.run(b, ref, info)
+            need = eng.pca_project_workspace_bytes(b.n_frames, n_sel, k)
+            if need and (work is None or need > work.numel() * 8):  # not monotone in the batch size
+                work = eng.empty((need + 7) // 8)
+            eng.pca_project(b.ptr, b.fstride, b.n_frames, n_sel, b.sel, x, info if x is not None else None,
+                            mean, comp, k, out[done:done + b.n_frames], work if need else None)
+            done += b.n_frames
+            b.done()
+        if done != n_frames:
+            raise RuntimeError(f"the source yielded {done} of {n_frames} frames")
+        torch.cuda.current_stream(eng.device).synchronize()
+        return out if as_tensor else out.cpu().numpy()
+
+
 class PCA:
     """Principal component analysis of a trajectory's selected coordinates.
 
@@ -343,24 +463,7 @@ class PCA:
     def _refuse_transform(self, atomgroup, what: str = "PCA.transform") -> None:
         """What ``transform`` -- and ``solver="matrix_free"``, which reads the
         trajectory the same way (``what``) -- refuses, before any launch."""
-        import torch
-
-        from . import parallel
-        from .sources import DeviceSource
-
-        one_device = _ONE_DEVICE.replace("PCA.transform", what)
-        r = self._rmsf
-        for x in (r._input, atomgroup):
-            if isinstance(x, (list, tuple)):
-                raise NotImplementedError(one_device + "with gpus= or a list of shards")
-        if r.gpus is not None:
-            raise NotImplementedError(one_device + "with gpus= or a list of shards")
-        x = r._input if atomgroup is None else atomgroup
-        if (isinstance(x, DeviceSource) and x.layout == "soa") or (
-                isinstance(x, torch.Tensor) and x.device.type == "cuda" and r.layout == "soa"):
-            raise NotImplementedError(_PLANES.replace("PCA.transform", what))
-        if parallel.world()[1] > 1:
-            raise NotImplementedError(one_device + "under torch.distributed with more than one rank")
+        refuse_one_device(self._rmsf, atomgroup, what)
 
     def transform(self, atomgroup=None, n_components: int | None = None, start=None, stop=None, step=None,
                   frames=None, as_tensor: bool = False):
@@ -393,93 +496,5 @@ class PCA:
         ``layout="soa"`` planes and a ``torch.distributed`` world of more than
         one rank are NotImplementedError; a projection over half the free HBM
         is a MemoryError."""
-        comps = self.results.get("p_components")
-        if comps is None:
-            raise ValueError("PCA.transform needs the components: call run() first (the non-root ranks of a "
-                             "reduce-to-root merge hold none)")
-        k_total = int(comps.shape[1])
-        k = k_total if n_components is None else int(n_components)
-        if not 1 <= k <= k_total:
-            raise ValueError(f"n_components must be in 1..{k_total}, got {n_components}")
-        self._refuse_transform(atomgroup)
-        r = self._rmsf
-        last = r._last_run
-        if last is None:
-            # results filled in by hand (components kept from an earlier run): without alignment there is
-            # no superposition to repeat, and the PCA's own input can be projected
-            if r.align is not None:
-                raise ValueError("PCA.transform needs the superposition of run(): these results were not computed "
-                                 "by run() on this object")
-            last = {"source": None, "frames": None, "masses": None, "device": r.device, "exact": False,
-                    "ref": None, "refinfo": None}
-
-        import torch
-
-        from ._lib import RMSF_XFORM_DOUBLES
-        from .engine import Engine
-        from .pipeline import Superposer
-        from .rms import make_source
-        from .sources import DeviceSource, FrameList
-
-        eng = Engine(last["device"])
-        with torch.cuda.device(eng.device):
-            if atomgroup is None and last["source"] is None:
-                atomgroup = r._input
-            if atomgroup is None:
-                src = last["source"]
-                same = start is None and stop is None and step is None and frames is None
-                fl = last["frames"] if same else FrameList(src.n_traj, start, stop, step, frames=frames)
-            else:
-                src, _ = make_source(atomgroup, select=r.select, masses=r.masses, align=None,
-                                     batch_frames=r.batch_frames, layout=r.layout, group_masses=False)
-                fl = FrameList(src.n_traj, start, stop, step, frames=frames)
-            if isinstance(src, DeviceSource) and src.layout == "soa":
-                raise NotImplementedError(_PLANES)
-            n_sel = src.n_sel
-            if 3 * n_sel != comps.shape[0]:
-                raise ValueError(f"the input selects {n_sel} atoms, the components were computed for "
-                                 f"{comps.shape[0] // 3}")
-            n_frames = len(fl)
-            check_projection_memory(eng, n_frames, k)
-            out = eng.empty(n_frames, k)
-            if n_frames == 0:
-                return out if as_tensor else out.cpu().numpy()
-            mean = torch.as_tensor(np.ascontiguousarray(self.results.mean, dtype=np.float64).reshape(-1)).to(
-                eng.device)
-            comp = torch.as_tensor(np.ascontiguousarray(comps, dtype=np.float64)).to(eng.device)
-            max_batch = max(1, min(r.batch_frames or n_frames, n_frames))
-            aligned = r.align is not None
-            exact = bool(last["exact"])
-            ref, info = last["ref"], last["refinfo"]
-            m_dev, mass_total, sup, xf = None, float(n_sel), None, None
-            if aligned:
-                masses = last["masses"]
-                if masses is not None:
-                    m_np = np.ascontiguousarray(masses, dtype=np.float64)
-                    mass_total = float(m_np.sum())  # numpy's own sum, as the exact run's (pipeline._run_exact)
-                    m_dev = torch.as_tensor(m_np).to(eng.device)
-                if exact:
-                    xf = eng.empty(max_batch, RMSF_XFORM_DOUBLES)
-                else:
-                    sup = Superposer(eng, n_sel, max_batch, m_dev)
-            work, done = None, 0
-            for b in src.batches(fl, 0, n_frames, max_batch, eng.stream):
-                if b.pstride:
-                    raise NotImplementedError(_PLANES)
-                x = None
-                if aligned and exact:
-                    x = xf[:b.n_frames]
-                    eng.superpose_seq(b.ptr, b.fstride, b.n_frames, n_sel, b.sel, m_dev, mass_total, ref, info, x)
-                elif aligned:
-                    x = sup.run(b, ref, info)
-                need = eng.pca_project_workspace_bytes(b.n_frames, n_sel, k)
-                if need and (work is None or need > work.numel() * 8):  # not monotone in the batch size
-                    work = eng.empty((need + 7) // 8)
-                eng.pca_project(b.ptr, b.fstride, b.n_frames, n_sel, b.sel, x, info if x is not None else None,
-                                mean, comp, k, out[done:done + b.n_frames], work if need else None)
-                done += b.n_frames
-                b.done()
-            if done != n_frames:
-                raise RuntimeError(f"the source yielded {done} of {n_frames} frames")
-            torch.cuda.current_stream(eng.device).synchronize()
-            return out if as_tensor else out.cpu().numpy()
+        return project_on_components(self._rmsf, self.results.get("p_components"), self.results.get("mean"),
+                                     "PCA.transform", atomgroup, n_components, start, stop, step, frames, as_tensor)

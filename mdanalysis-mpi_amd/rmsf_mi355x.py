@@ -102,7 +102,19 @@ def main(argv=None) -> int:
                     help="--pca-transform: numpy.linalg.eigh on the host, or the first --n-components (<= 40) modes "
                          "by subspace iteration on the device: 'device' with the matrix staying in HBM, "
                          "'matrix_free' from the trajectory alone, with no 3n x 3n matrix (any number of atoms)")
+    ap.add_argument("--tica", default=None, metavar="OUT.npz",
+                    help="also run rmsf_amd.TICA on the same input with --align and write its eigenvalues, "
+                         "timescales, components [3n, K] and mean [n, 3] (one process only; K: --n-components, "
+                         "default every direction the covariance keeps)")
+    ap.add_argument("--tica-lag", type=int, default=None, metavar="L",
+                    help="--tica: the lag, in frames of the run's list")
     a = ap.parse_args(argv)
+    if bool(a.tica) != (a.tica_lag is not None):
+        ap.error("--tica OUT.npz and --tica-lag L go together")
+    if a.tica and a.tica_lag < 1:
+        ap.error("--tica-lag must be at least 1")
+    if a.tica and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--tica runs in one process (no torch.distributed launch)")
     if a.pca_transform and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--pca-transform runs in one process (no torch.distributed launch)")
     if a.pca_transform and a.merge == "scatter":
@@ -271,6 +283,15 @@ def main(argv=None) -> int:
         print(f"PCA projection of {proj.shape[0]} frames on {proj.shape[1]} components: the first holds "
               f"{pca.results.cumulated_variance[0]:.4f} of the variance", flush=True)
         np.save(a.pca_transform, proj)
+    if a.tica:
+        from rmsf_amd import TICA
+        tica_kw = {"select": dm_kw["select"], "masses": dm_kw["weights"]} if dm_kw else {}
+        tr = TICA(dm_input, a.tica_lag, align=align, ref_frame=a.ref_frame, n_components=a.n_components,
+                  **tica_kw).run().results
+        print(f"TICA at lag {tr.lag} over {tr.n_pairs} pairs of {tr.n_frames} frames, rank {tr.rank}: eigenvalues "
+              f"{np.array2string(tr.eigenvalues[:5], precision=6)}, timescales "
+              f"{np.array2string(tr.timescales[:5], precision=2)} frames", flush=True)
+        np.savez(a.tica, eigenvalues=tr.eigenvalues, timescales=tr.timescales, components=tr.components, mean=tr.mean)
     if rank == 0:
         print(f"RMSF over {len(rmsf)} atoms: mean {rmsf.mean():.6f} A, max {rmsf.max():.6f} A", flush=True)
         if a.out:
