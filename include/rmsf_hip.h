@@ -539,7 +539,7 @@ int rmsf_covariance_finish(double *d_cov, int64_t ld, const double *d_t1,
 
 /* ---- time-lagged co-moment (the contraction of TICA) -----------------------
  * The covariance contraction with its two operands apart in time, on the f64
- * matrix cores (csrc/lagged.hip).  Coordinate index i = 3 a + c over the
+ * matrix cores (csrc/covariance.hip).  Coordinate index i = 3 a + c over the
  * selection's order, p and d as rmsf_covariance_accumulate has them.  Pair q
  * of the batch is frame q of operand A (d_xyz_a, frame_stride_a, records
  * d_xform_a) and frame q of operand B (d_xyz_b, frame_stride_b, d_xform_b);

@@ -1,4 +1,4 @@
-// dense_f64.h -- what the dense f64 MFMA contractions (covariance.hip, lagged.hip,
+// dense_f64.h -- what the dense f64 MFMA contractions (covariance.hip,
 // pairwise.hip, pca_project.hip, pca_backproject.hip, eigen_block.hip) have in common: the workgroup's shape, the
 // 3 x 3 block of v_mfma_f64_16x16x4_f64 and its wave-order sum, the split-K
 // plan and the upper block triangle's pair index.  Staging, pipelining and

@@ -86,9 +86,9 @@ __device__ __forceinline__ void mfma_3xn(f64x4 (&acc)[3][3], const double (&a)[3
 }
 
 // One workgroup: atoms [16 blockIdx.x, +16), frames [blockIdx.y ks_frames,
-// ...).  Staging (k_cov_tiles' operand A): lane (tid & 15) owns one atom of
-// the tile, (tid >> 4) one of 16 frames per pass; its three deviations go to
-// sm[k][3 atom + c].  MFMA operands (16x16x4 f64, dense_f64.h): lane l holds
+// ...).  Staging (k_comoment_tiles' operand A): lane (tid & 15) owns one atom
+// of the tile, (tid >> 4) one of 16 frames per pass; its three deviations go
+// to sm[k][3 atom + c].  MFMA operands (16x16x4 f64, dense_f64.h): lane l holds
 // A[i = l & 15][k = l >> 4] = the deviation of coordinate 16 t + i in staged
 // frame k, one of 16 consecutive doubles of row k, and B[k = l >> 4][j = l &
 // 15] = P's row of frame k, 16 consecutive doubles of d_p; the result D has
@@ -146,20 +146,12 @@ __global__ __launch_bounds__(kBlock, 2) void k_bproj_tiles(const float *__restri
   // MFMAs, so the global-load latency runs under the matrix pipe; the floats
   // become deviations in LDS after, and the records are parked in LDS (sxf)
   // once the MFMAs are issued, where the 16 lanes of a frame read them as a
-  // broadcast (k_cov_tiles' scheme).
-  constexpr int kRecLoads = (kKT * kRec + kBlock - 1) / kBlock;
+  // broadcast (load_records / park_records, rmsf_device.h).
   float raw[kPasses][3];
-  double recv[kRecLoads];
+  double recv[rec_loads(kKT, kBlock)];
   double bn[kSteps][NT];
   auto prefetch = [&](int64_t fb) {
-    if (ALIGN) {
-#pragma unroll
-      for (int r = 0; r < kRecLoads; ++r) {
-        const int e = (r * kBlock + tid) % (kKT * kRec);  // (the last round wraps: its extra lanes reload)
-        const int64_t f = fb + e / kRec;
-        recv[r] = xform[(f < f1 ? f : f1 - 1) * kXform + e % kRec];
-      }
-    }
+    if (ALIGN) load_records<kKT, kBlock>(recv, xform, fb, f1, tid);
 #pragma unroll
     for (int s = 0; s < kSteps; ++s) {
       const int64_t f = fb + (kKT / kWaves) * wave + 4 * s + (lane >> 4);
@@ -174,17 +166,8 @@ __global__ __launch_bounds__(kBlock, 2) void k_bproj_tiles(const float *__restri
       raw[pass][0] = q[0], raw[pass][1] = q[1], raw[pass][2] = q[2];
     }
   };
-  auto park_records = [&]() {
-    if (ALIGN) {
-#pragma unroll
-      for (int r = 0; r < kRecLoads; ++r) {
-        const int e = r * kBlock + tid;
-        if (e < kKT * kRec) sxf[e] = recv[r];
-      }
-    }
-  };
   prefetch(f0);
-  park_records();
+  if (ALIGN) park_records<kKT, kBlock>(sxf, recv, tid);
   __syncthreads();
 
   for (int64_t fb = f0; fb < f1; fb += kKT) {
@@ -219,7 +202,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_bproj_tiles(const float *__restri
       const double av[3] = {ra[0], ra[16], ra[32]};
       mfma_3xn(acc, av, b[s]);
     }
-    park_records();  // this stage's were last read before the barrier above
+    if (ALIGN) park_records<kKT, kBlock>(sxf, recv, tid);  // this stage's were last read before the barrier above
     __syncthreads();
   }
 

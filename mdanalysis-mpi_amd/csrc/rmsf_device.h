@@ -37,6 +37,36 @@ __device__ __forceinline__ void apply_xform(float &x, float &y, float &z, const 
   z = (float)((double)r2 + rc2);
 }
 
+// A stage's transform records on their way to LDS, in the dense sweeps that
+// stage KT frames at a time with a workgroup of BLOCK threads: the kRec
+// doubles apply_xform reads of frames [fb, fb + KT) -- a frame past the
+// range's end reads frame f1 - 1 -- are loaded into registers, 1.5 doubles a
+// lane at KT = 32 and BLOCK = 256, ahead of the MFMAs that hide the latency,
+// and parked in sxf[KT][kRec] once those are issued, where the 16 lanes of a
+// frame read them as a broadcast.
+constexpr int rec_loads(int kt, int block) { return (kt * kRec + block - 1) / block; }  // doubles a lane
+
+template <int KT, int BLOCK>
+__device__ __forceinline__ void load_records(double (&recv)[rec_loads(KT, BLOCK)], const double *__restrict__ xform,
+                                             int64_t fb, int64_t f1, int tid) {
+#pragma unroll
+  for (int r = 0; r < rec_loads(KT, BLOCK); ++r) {
+    const int e = (r * BLOCK + tid) % (KT * kRec);  // (the last round wraps: its extra lanes reload)
+    const int64_t f = fb + e / kRec;
+    recv[r] = xform[(f < f1 ? f : f1 - 1) * kXform + e % kRec];
+  }
+}
+
+template <int KT, int BLOCK>
+__device__ __forceinline__ void park_records(double *sxf, const double (&recv)[rec_loads(KT, BLOCK)],
+                                             int tid) {
+#pragma unroll
+  for (int r = 0; r < rec_loads(KT, BLOCK); ++r) {
+    const int e = r * BLOCK + tid;
+    if (e < KT * kRec) sxf[e] = recv[r];
+  }
+}
+
 // ---------------------------------------------------------------------------
 // QCP: the published quaternion-characteristic-polynomial algorithm
 // (D. Theobald, Acta Cryst A 61:478, 2005; P. Liu et al., J Comput Chem

@@ -411,7 +411,7 @@ class Engine:
             raise ValueError("covariance_finish: buffer sizes")
         call("rmsf_covariance_finish", cov.data_ptr(), cov.stride(0), t1.data_ptr(), n_coord, n_frames, self.stream)
 
-    # -- time-lagged co-moment (csrc/lagged.hip) -------------------------------
+    # -- time-lagged co-moment (csrc/covariance.hip) ---------------------------
     def lagged_comoment_workspace_bytes(self, n_sel: int, n_pairs: int) -> int:
         return int(self.lib.rmsf_lagged_comoment_workspace_bytes(n_sel, n_pairs))
 

@@ -15,8 +15,8 @@ pairs, d(t) the deviations from a shift near the data, and the reversible
     Ct v = lambda C0 v
 
 M0 and T are two calls of the covariance kernel (csrc/covariance.hip), one
-per window, into one matrix; S is csrc/lagged.hip, the same contraction on
-the f64 matrix cores with its operands ``lag`` frames apart, and all three
+per window, into one matrix; S is that file's tile body again, the same
+contraction on the f64 matrix cores with its operands ``lag`` frames apart, and all three
 read the superposed coordinates the Welford sweep read, with no aligned copy
 of the trajectory.  The generalised eigenproblem is solved on the host
 (``tica_from_comoments``, numpy); ``TICA.transform`` is ``PCA.transform``'s

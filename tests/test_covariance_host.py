@@ -94,8 +94,8 @@ def _pair_to_tiles():
 
 @pytest.mark.parametrize("n_tiles", [1, 2, 3, 22, 209, 256])
 def test_pair_to_tiles_is_the_upper_triangle_in_row_order(n_tiles):
-    """The tile mapping of k_cov_tiles, k_cov_fold, k_pw_tiles and k_pw_fold
-    (csrc/dense_f64.h), on the host: a wrong (I, J) there is an out-of-bounds
+    """The tile mapping of k_comoment_tiles, k_comoment_fold, k_pw_tiles and
+    k_pw_fold (csrc/dense_f64.h), on the host: a wrong (I, J) there is an out-of-bounds
     store."""
     mapped = _pair_to_tiles()
     p = 0

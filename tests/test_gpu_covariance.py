@@ -118,7 +118,7 @@ def run_rmsf(n_sel: int, n_frames: int, gathered: bool, align, exact, batch_fram
 
 
 # ---- 1. engine level, no alignment -----------------------------------------
-# (500, 40): 528 tile pairs and two stages -- k_cov_tiles straight to d_cov over more than one stage
+# (500, 40): 528 tile pairs and two stages -- k_comoment_tiles straight to d_cov over more than one stage
 ENGINE_SHAPES = [(1, 1, None), (5, 3, None), (16, 4, None), (17, 5, None), (214, 67, None), (341, 300, 128),
                  (500, 40, None)]
 

@@ -1,5 +1,5 @@
-"""GPU tier of TICA: the lagged co-moment kernel (csrc/lagged.hip, f64 MFMA
-over the full square of tiles), its finish, and ``TICA`` end to end, against
+"""GPU tier of TICA: the lagged co-moment kernel (csrc/covariance.hip's tile
+body over the full square of tiles), its finish, and ``TICA`` end to end, against
 the reversible estimator restated in numpy f64 (tests/test_tica_host.py::
 reversible_comoments) on raw frames or on frames aligned by the oracle's
 ``align_frame_``.  Data: tests/test_tica_host.py::make_lagged_traj.
@@ -78,6 +78,50 @@ def test_engine_lagged_comoment_unaligned(n_sel, n_frames, lag, batch, gathered)
     # the same bits from a second identical run
     again = engine_lagged(eng, x, sel_dev, shift, n_sel, n_frames, lag, batch).cpu().numpy()
     assert np.array_equal(bits(again), bits(got))
+
+
+# (n_sel, F): one tile; two tiles a side with an atom in the second; three tiles with a ragged stage
+SAME_OPERAND_SHAPES = [(5, 3), (17, 32), (33, 20)]
+
+
+@pytest.mark.parametrize("aligned", [False, True], ids=["unaligned", "aligned"])
+@pytest.mark.parametrize("gathered", [False, True], ids=["dense", "gathered"])
+@pytest.mark.parametrize("n_sel,n_frames", SAME_OPERAND_SHAPES)
+def test_lagged_with_one_operand_twice_is_the_covariance_kernel(n_sel, n_frames, gathered, aligned):
+    """The two instantiations of the co-moment tile body against each other:
+    with B = A (pointer, stride, records) the time-lagged kernel stages the
+    doubles the positional kernel stages, contracts them in the same MFMA order
+    and sums the waves alike, so at F <= 32 -- one stage, one frame range in
+    both plans -- S equals C bit for bit on the tile pairs J >= I that the
+    positional kernel writes, and S is symmetric in its bits."""
+    import torch
+
+    from rmsf_amd.engine import Engine
+    from test_gpu_pca_backproject import superposed
+    eng = Engine(torch.device("cuda", 0))
+    assert eng.covariance_workspace_bytes(n_sel, n_frames) == 0
+    assert eng.lagged_comoment_workspace_bytes(n_sel, n_frames) == 0
+    n_atoms, sel = selection(n_sel, gathered)
+    x = torch.tensor(make_lagged_traj(n_atoms, n_frames), device="cuda:0")
+    sel_dev = eng.sel_tensor(sel)
+    xf, info = superposed(eng, x, sel_dev, n_sel, n_frames) if aligned else (None, None)
+    rows = x[0] if sel_dev is None else x[0][sel_dev.long()]
+    shift = rows.reshape(-1).double().contiguous()
+    n = 3 * n_sel
+    s, c, t1 = eng.zeros(n, n), eng.zeros(n, n), eng.zeros(n)
+    eng.lagged_comoment_accumulate(x.data_ptr(), x.stride(0), x.data_ptr(), x.stride(0), n_frames, n_sel, sel_dev,
+                                   xf, xf, info, shift, s)
+    eng.covariance_accumulate(x.data_ptr(), x.stride(0), n_frames, n_sel, sel_dev, xf, info, shift, c, t1)
+    torch.cuda.synchronize()
+    s, c = s.cpu().numpy(), c.cpu().numpy()
+    tile = np.arange(n) // 48
+    written = tile[None, :] >= tile[:, None]                # whole 48 x 48 tile pairs J >= I
+    assert np.any(s != 0.0)
+    differ = int((bits(s)[written] != bits(c)[written]).sum())
+    print(f"B = A ({n_sel}, {n_frames}) gathered={gathered} aligned={aligned}: {differ} of {int(written.sum())} "
+          f"elements differ")
+    assert differ == 0
+    assert_symmetric_bits(s)
 
 
 # ---- 2. finish --------------------------------------------------------------

@@ -7,7 +7,10 @@ checkouts (a refactor's proof: csrc/dense_f64.h, rmsf_device.h::qcp_lambda).
 
 ``dump`` imports rmsf_amd from the checkout at PATH (built there), runs seeded
 inputs through its ``Engine`` and saves the raw outputs: covariance
-(accumulate + finish), pairwise RMSD (centres + rmsd, cutoff 0), its neighbour
+(accumulate + finish), the time-lagged co-moment (S after accumulate, M after
+finish; dense / gathered, unaligned / aligned on superpose's records, one case
+over three calls), pca_backproject (overwriting and accumulating), pairwise
+RMSD (centres + rmsd, cutoff 0), its neighbour
 bits and counts (pairwise_adjacency within the median distance), the cross RMSD
 matrix (centres per side + cross_rmsd, cutoff 0), pca_project, qcp_batch, and
 the transform records of superpose and superpose_seq.
@@ -29,7 +32,14 @@ CROSS_SHAPES = [(1, 1, 3), (17, 33, 33), (33, 5, 31), (3, 5, 5000), (50, 40, 214
 # tests/test_gpu_pca_project.py::ENGINE_SHAPES as (n_sel, n_frames, k)
 PROJ_SHAPES = [(1, 1, 1), (5, 3, 2), (16, 16, 16), (17, 17, 17), (17, 33, 51), (214, 67, 10), (341, 300, 7),
                (5000, 5, 3)]
-SUPERPOSE_SHAPE = (214, 67)                                                        # (n_sel, n_frames)
+# (n_sel, n_frames, lag, pairs a call): one pair range, the tile edge either side of 16 atoms, a tail stage,
+# split-K with a fold (whole, and over three calls), and at 25 tiles a side the direct path
+LAG_SHAPES = [(5, 3, 1, None), (16, 33, 1, None), (17, 40, 7, None), (214, 67, 10, None), (341, 300, 5, None),
+              (341, 300, 31, 128), (400, 45, 3, None)]
+# tests/test_gpu_pca_backproject.py::ENGINE_SHAPES as (n_sel, n_frames, cols)
+BPROJ_SHAPES = [(1, 1, 1), (5, 3, 2), (16, 32, 16), (17, 33, 17), (33, 31, 33), (214, 67, 48), (341, 300, 7),
+                (5, 5000, 3), (5000, 5, 48)]
+SUPERPOSE_SHAPE = (214, 67)                                                       # (n_sel, n_frames)
 
 
 def trajectory(n_atoms, n_frames):
@@ -170,6 +180,49 @@ def dump(tree, out_path):
         proj = torch.full((n_frames, k), float("nan"), dtype=torch.float64, device=dev)
         eng.pca_project(x.data_ptr(), x.stride(0), n_frames, n_sel, sel_dev, xf, info, mean, v, k, proj, work)
         out[f"proj_{n_sel}x{n_frames}x{k}_g{int(gathered)}_a{int(aligned)}"] = proj.cpu().numpy()
+
+    # the time-lagged co-moment: S before the finish, M after (t = operand A's T1 plus operand B's, what TICA gives it)
+    for (n_sel, n_frames, lag, batch), gathered, aligned in itertools.product(LAG_SHAPES, (False, True),
+                                                                                (False, True)):
+        x, sel_dev = case(n_sel, n_frames, gathered)
+        xf, info = records(x, sel_dev, n_sel, n_frames) if aligned else (None, None)
+        n, n_pairs = 3 * n_sel, n_frames - lag
+        rows = x[0] if sel_dev is None else x[0][sel_dev.long()]
+        shift = rows.reshape(-1).double().contiguous()
+        s, cov, t = eng.zeros(n, n), eng.zeros(n, n), eng.zeros(n)
+        for k in range(0, n_pairs, batch or n_pairs):      # with a batch: several calls, offset pointers
+            nb = min(batch or n_pairs, n_pairs - k)
+            need = max(eng.lagged_comoment_workspace_bytes(n_sel, nb), eng.covariance_workspace_bytes(n_sel, nb))
+            work = eng.empty(need // 8) if need else None
+            a, b = x.data_ptr() + 4 * k * x.stride(0), x.data_ptr() + 4 * (k + lag) * x.stride(0)
+            xa = None if xf is None else xf[k:k + nb]
+            xb = None if xf is None else xf[k + lag:k + lag + nb]
+            eng.lagged_comoment_accumulate(a, x.stride(0), b, x.stride(0), nb, n_sel, sel_dev, xa, xb, info, shift, s,
+                                           work)
+            eng.covariance_accumulate(a, x.stride(0), nb, n_sel, sel_dev, xa, info, shift, cov, t, work)
+            eng.covariance_accumulate(b, x.stride(0), nb, n_sel, sel_dev, xb, info, shift, cov, t, work)
+        key = f"lag_{n_sel}x{n_frames}_l{lag}_b{batch or 0}_g{int(gathered)}_a{int(aligned)}"
+        out[key + "_s"], out[key + "_t"] = s.cpu().numpy(), t.cpu().numpy()
+        eng.lagged_comoment_finish(s, t, n, 2 * n_pairs)
+        out[key] = s.cpu().numpy()
+
+    # pca_backproject, overwriting and accumulating onto a seeded Y
+    for (n_sel, n_frames, cols), gathered, aligned in itertools.product(BPROJ_SHAPES, (False, True), (False, True)):
+        x, sel_dev = case(n_sel, n_frames, gathered)
+        xf, info = records(x, sel_dev, n_sel, n_frames) if aligned else (None, None)
+        rng = np.random.default_rng(13 * n_sel + cols)
+        p = torch.tensor(rng.normal(size=(n_frames, cols)), device=dev)
+        y0 = torch.tensor(rng.normal(size=(3 * n_sel, cols)), device=dev)
+        xs = x if sel_dev is None else x.index_select(1, sel_dev.long())
+        mean = xs.double().mean(dim=0).reshape(-1).contiguous()
+        need = eng.pca_backproject_workspace_bytes(n_frames, n_sel, cols)
+        work = eng.empty(need // 8) if need else None
+        for accumulate in (False, True):
+            y = y0.clone()
+            eng.pca_backproject(x.data_ptr(), x.stride(0), n_frames, n_sel, sel_dev, xf, info, mean, p, cols, y,
+                                accumulate, work)
+            out[f"bproj_{n_sel}x{n_frames}x{cols}_g{int(gathered)}_a{int(aligned)}_acc{int(accumulate)}"] = \
+                y.cpu().numpy()
 
     # qcp_batch: tests/golden/qcp_kat.npz's pair, then seeded 50-atom pairs
     kat = np.load(os.path.join(tree, "tests", "golden", "qcp_kat.npz"))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Timing of the time-lagged co-moment (csrc/lagged.hip) and of TICA on one
-MI355X.
+"""Timing of the time-lagged co-moment (csrc/covariance.hip, the LAGGED
+instantiation of its tile body) and of TICA on one MI355X.
 
 Per shape (selected atoms x frames, HBM-resident f32 rows, lag 10):
   * ``kernel``: rmsf_lagged_comoment_accumulate + rmsf_lagged_comoment_finish
