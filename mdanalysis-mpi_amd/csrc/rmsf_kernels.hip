@@ -3471,6 +3471,17 @@ int ref_centre_seq(const float *d_frame, const double *d_avg, double div, int64_
 
 extern "C" {
 
+// (for the tests: the constants the serial chains are built from, so their
+// shapes follow the kernel -- atoms per group of row_add32, atoms per block,
+// the launch forms' chain counts, the reference's grid-wide switch)
+RMSF_EXPORT void rmsf_internal_seq_chain_layout(int64_t *out5) {
+  out5[0] = 32;
+  out5[1] = kSeqBlk;
+  out5[2] = kSeqPcMax;
+  out5[3] = kSeqReserveMax;
+  out5[4] = kRefGridMin;
+}
+
 RMSF_EXPORT int rmsf_reference_centre_sequential(const float *d_frame, const double *d_avg, double avg_divisor,
                                                  int64_t n_sel, const int32_t *d_sel, const double *d_masses,
                                                  double mass_total, double *d_avg_out, double *d_ref,

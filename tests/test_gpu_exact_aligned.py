@@ -24,6 +24,7 @@ import torch
 from conftest import GOLDEN, PKG, ROOT
 from oracle import rmsf_oracle as O
 from oracle import synth as SY
+from test_gpu_exact_chains import chain_layout
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-6
@@ -174,12 +175,21 @@ def test_exact_aligned_vs_oracle(ci, where):
         _same(r.average, want["average"], "average")
 
 
+_, _B, _P, _R, _ = chain_layout()  # the serial chains' block and launch forms, as the kernel was built
+
+
 @pytest.mark.parametrize("gathered", [False, True])
-@pytest.mark.parametrize("n_sel", [1, 2, 3, 63, 64, 65, 255, 256, 257, 511, 512, 513, 769])
+@pytest.mark.parametrize("n_sel", sorted({1, 2, 3, 63, 64, 65, 255, 256, 257, 511, 512, 513, 769,
+                                          _B - 1, _B, _B + 1, 2 * _B, 2 * _B + 1}))
 def test_exact_aligned_block_edges(n_sel, gathered):
-    """The serial sums run 256 atoms per block in one wave (wave_seq_sum:
-    whole blocks, a two-block loop, a partial last block); selections on
-    either side of every block edge equal the oracle bit for bit."""
+    """Selections on either side of every block edge equal the oracle bit
+    for bit.  The serial sums (wave_seq_sum / pc_seq_sum: whole blocks, a
+    partial last block) run kSeqBlk atoms per block -- B - 1, B, B + 1, 2 B
+    and 2 B + 1 here, B read from the library; the counts up to 769 are one
+    ragged block of the chains and the edges of k_accum_seq's 256-thread
+    workgroups (and of a wave's 64 lanes).  At these 6 frames every chain
+    launch is the two-wave form; tests/test_gpu_exact_chains.py runs the
+    other forms and the chains' raw sums."""
     from rmsf_amd import RMSF
     from rmsf_amd.synth import motion_table
     nf = 6
@@ -194,6 +204,40 @@ def test_exact_aligned_block_edges(n_sel, gathered):
         _same(r.mean, want["mean"], f"mean {align}")
         if align == "average":
             _same(r.average, want["average"], "average")
+
+
+@pytest.fixture(scope="module")
+def one_wave_case():
+    from rmsf_amd.synth import motion_table
+    n_sel, nf = 2 * _B + 1, 90
+    n_atoms = 3 * n_sel + 1
+    traj = SY.frames(65, n_atoms, 0, nf, motion_table(66, nf))
+    sel = np.arange(1, n_atoms, 3)[:n_sel]
+    m = np.random.default_rng(67).uniform(1.0, 16.0, n_sel)
+    return traj, sel, m, O.rmsf_script(traj, sel, m, size=1, align="average")
+
+
+@pytest.mark.parametrize("batch", [None, 60])
+def test_exact_aligned_one_wave_chains(one_wave_case, batch):
+    """A whole run whose chain launches take the one-wave forms over more
+    than one block: 2 B + 1 gathered atoms (two whole blocks and an atom), 90
+    frames.  In one batch the InnerProduct's 900 chains run unreserved (the
+    form of a 100k-atom, 100-frame run); in batches of 60 they run with
+    reserved LDS, then the last 30 frames two-wave.  The oracle bit for bit.
+    (An end-to-end result sees a lost or doubled atom, not a wrong order: a
+    build whose wave_seq_sum added the two blocks of its loop in the other
+    order still passed this, because the last bits of A seldom flip an f32
+    rounding of an aligned coordinate.  The order is
+    tests/test_gpu_exact_chains.py's to pin, on the raw sums.)"""
+    from rmsf_amd import RMSF
+    traj, sel, m, want = one_wave_case
+    assert 10 * 90 > _R and _P < 10 * 60 <= _R and 10 * 30 <= _P  # the forms named above
+    r = RMSF(torch.tensor(traj, device="cuda"), select=sel, masses=m, align="average", exact=True,
+             batch_frames=batch).run().results
+    _same(r.rmsf, want["rmsf"], "rmsf")
+    _same(r.mean, want["mean"], "mean")
+    _same(r.sumsquares, want["m2"], "sumsquares")
+    _same(r.average, want["average"], "average")
 
 
 @pytest.mark.parametrize("overlap", [False, True])
