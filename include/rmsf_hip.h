@@ -949,6 +949,87 @@ int rmsf_cluster_dbscan_host(const double *h_m, int64_t n, int64_t ld,
                              int32_t *h_label, uint64_t *h_core,
                              int32_t *h_n_clusters);
 
+/* ---- contacts: distances between atoms within a frame (csrc/contacts.hip) ---
+ * One rule everywhere.  Coordinates are f32 as stored;
+ *   dx = (double)xa - (double)xb, dy and dz likewise,
+ *   d2 = (dx*dx + dy*dy) + dz*dz with no FMA, d = sqrt(d2) correctly rounded,
+ * and a pair is in contact iff d <= radius.  A NaN is never a contact, so an
+ * atom with a non-finite coordinate in a frame loses its pairs in that frame
+ * and nothing else changes.  No periodic images: the library reads no boxes.
+ * rmsf_contact_threshold_sq(radius): the largest double t with sqrt(t) <=
+ *   radius (NaN unless radius is positive and finite).  sqrt is monotone, so
+ *   d2 <= t is the same predicate and the device entries take no root a pair.
+ * Frames are d_xyz + f * frame_stride floats, f < n_frames, each holding
+ * n_atoms rows of 3 floats (frame_stride >= 3 n_atoms).  An index array names
+ * rows of a frame, NULL the rows 0..n-1.  Every index array has a device copy
+ * the kernels read and a host copy h_* the call checks against its bound
+ * before any launch (NULL: the caller vouches for it).
+ * rmsf_contact_counts: d_counts[i][j] (int32 [n_a][ld], ld >= n_b; columns at
+ *   or past n_b are not written) = the number of frames in which rows a_i and
+ *   b_j are in contact.  symmetric != 0: A is B (n_a == n_b, d_idx_a ==
+ *   d_idx_b); only tiles on or above the diagonal are computed, each mirrored,
+ *   the diagonal like any other entry.  A workgroup owns a tile of pairs and a
+ *   run of frames staged through LDS a chunk at a time; where the tiles are
+ *   few the frames are split across workgroups and the splits meet in
+ *   d_counts by integer atomicAdd after one zeroing launch -- exact in any
+ *   order, the same bytes every run.  rmsf_contact_counts_plan reports what
+ *   the launcher chooses: the tile's edges, the frame chunk and the number of
+ *   splits (host only).  rmsf_contact_counts_workspace_bytes is what d_work
+ *   must hold: 0 as the splits are combined now, d_work may be NULL.
+ * rmsf_contact_fraction: pairs p < n_pairs of rows[pair_a[p]] and
+ *   rows[pair_b[p]], where d_rows[n_rows] are the frame's rows the pairs use
+ *   (staged in LDS once a frame where they fit) and pair_a / pair_b positions
+ *   in it.  d_n_contacts[f] (int32) = the pairs in contact at radius in frame
+ *   f, and d_q[f] (f64) by method:
+ *     RMSF_CONTACT_HARD_CUT, RMSF_CONTACT_RADIUS_CUT  n_contacts / n_pairs,
+ *       one f64 division; d_r0 is not read;
+ *     RMSF_CONTACT_SOFT_CUT  (sum over p of 1 / (1 + exp(beta * (d -
+ *       lambda_constant * r0[p])))) / n_pairs, the argument formed as written;
+ *       each lane sums its pairs in order and the lanes are summed by a fixed
+ *       tree: the same bits every run.
+ * The _host entries are the definition in plain C++ on host pointers (sqrt a
+ * pair, soft_cut summed in pair order) and touch no device.
+ * RMSF_EINVAL before any launch: n_pairs < 1, an index out of range, a radius
+ * that is not positive and finite, an unknown method, a NULL or a size out of
+ * range (frames, rows and pairs up to INT32_MAX).                            */
+#define RMSF_CONTACT_HARD_CUT 0
+#define RMSF_CONTACT_RADIUS_CUT 1
+#define RMSF_CONTACT_SOFT_CUT 2
+double rmsf_contact_threshold_sq(double radius);
+int rmsf_contact_counts_plan(int64_t n_a, int64_t n_b, int64_t n_frames,
+                             int symmetric, int32_t *tile_a, int32_t *tile_b,
+                             int32_t *frame_chunk, int32_t *n_splits);
+size_t rmsf_contact_counts_workspace_bytes(int64_t n_a, int64_t n_b,
+                                           int64_t n_frames, int symmetric);
+int rmsf_contact_counts(const float *d_xyz, int64_t frame_stride,
+                        int64_t n_frames, int64_t n_atoms,
+                        const int32_t *d_idx_a, const int32_t *h_idx_a,
+                        int64_t n_a, const int32_t *d_idx_b,
+                        const int32_t *h_idx_b, int64_t n_b, int symmetric,
+                        double radius, int32_t *d_counts, int64_t ld,
+                        void *d_work, size_t work_bytes, void *stream);
+int rmsf_contact_counts_host(const float *h_xyz, int64_t frame_stride,
+                             int64_t n_frames, int64_t n_atoms,
+                             const int32_t *h_idx_a, int64_t n_a,
+                             const int32_t *h_idx_b, int64_t n_b, double radius,
+                             int32_t *h_counts, int64_t ld);
+int rmsf_contact_fraction(const float *d_xyz, int64_t frame_stride,
+                          int64_t n_frames, int64_t n_atoms, int64_t n_rows,
+                          const int32_t *d_rows, const int32_t *h_rows,
+                          const int32_t *d_pair_a, const int32_t *d_pair_b,
+                          const int32_t *h_pair_a, const int32_t *h_pair_b,
+                          const double *d_r0, int64_t n_pairs, double radius,
+                          int method, double beta, double lambda_constant,
+                          double *d_q, int32_t *d_n_contacts, void *stream);
+int rmsf_contact_fraction_host(const float *h_xyz, int64_t frame_stride,
+                               int64_t n_frames, int64_t n_atoms,
+                               int64_t n_rows, const int32_t *h_rows,
+                               const int32_t *h_pair_a, const int32_t *h_pair_b,
+                               const double *h_r0, int64_t n_pairs,
+                               double radius, int method, double beta,
+                               double lambda_constant, double *h_q,
+                               int32_t *h_n_contacts);
+
 /* ---- qcprot.CalcRMSDRotationalMatrix (RMSF.py:48) --------------------------
  * Batched QCP on device: A[n][9], E0[n], atom counts N[n] -> rot[n][9],
  * rmsd[n].  Exposed for the upstream known-answer test.                      */

@@ -32,6 +32,10 @@ Public surface (mirrors the reference's names):
     time-lagged covariance of the (aligned) coordinates, the latter on the f64 matrix cores with its two
     operands ``lag`` frames apart: ``TICA(traj, lag=10).run().results.timescales`` / ``.components``;
     ``TICA.transform`` projects on them as ``PCA.transform`` does
+  * ``Contacts`` / ``ContactMap`` -- distances between atoms within a frame: the fraction of native
+    contacts Q(t), named as MDAnalysis.analysis.contacts.Contacts names it, and the count of frames in
+    which each pair of two selections touches; ``contact_threshold_sq`` is the squared cutoff the device
+    compares against.  No periodic boundary conditions
 """
 from ._lib import RmsfEmptyError, RmsfError, load as load_library
 from .parallel import blocks
@@ -43,8 +47,12 @@ from .pca import PCA, cosine_content, cumulative_overlap, pca_from_comoment, rms
 from .distances import CrossDistanceMatrix, DiffusionMap, DistanceMatrix, discrete_frechet, hausdorff
 from .clustering import DBSCAN, Cluster
 from .tica import TICA, tica_from_comoments
+from .contacts import ContactMap, Contacts, contact_threshold_sq
 
 __all__ = [
+    "ContactMap",
+    "Contacts",
+    "contact_threshold_sq",
     "TICA",
     "tica_from_comoments",
     "RMSF",

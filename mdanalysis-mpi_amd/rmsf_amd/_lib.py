@@ -27,6 +27,9 @@ ABI_VERSION = 4
 RMSF_PAIR_NEWTON = 0  # how rmsf_pair_lambda_host found a pair's lambda
 RMSF_PAIR_JACOBI = 1
 RMSF_PAIR_ZERO = 2
+RMSF_CONTACT_HARD_CUT = 0  # rmsf_contact_fraction's methods
+RMSF_CONTACT_RADIUS_CUT = 1
+RMSF_CONTACT_SOFT_CUT = 2
 
 
 class RmsfError(RuntimeError):
@@ -143,6 +146,17 @@ SIGNATURES = {
     "rmsf_cluster_dbscan_workspace_bytes": (c_size_t, [c_int64]),
     "rmsf_cluster_dbscan": (c_int, [P, c_int64, c_int64, P, c_int64, P, P, P, P, P, c_size_t, P]),
     "rmsf_cluster_dbscan_host": (c_int, [P, c_int64, c_int64, c_double, c_int64, P, P, P]),
+    "rmsf_contact_threshold_sq": (c_double, [c_double]),
+    "rmsf_contact_counts_plan": (c_int, [c_int64, c_int64, c_int64, c_int, POINTER(c_int32), POINTER(c_int32),
+                                         POINTER(c_int32), POINTER(c_int32)]),
+    "rmsf_contact_counts_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
+    "rmsf_contact_counts": (c_int, [P, c_int64, c_int64, c_int64, P, P, c_int64, P, P, c_int64, c_int, c_double, P,
+                                    c_int64, P, c_size_t, P]),
+    "rmsf_contact_counts_host": (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, c_double, P, c_int64]),
+    "rmsf_contact_fraction": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, P, P, P, P, P, c_int64, c_double,
+                                      c_int, c_double, c_double, P, P, P]),
+    "rmsf_contact_fraction_host": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, P, P, c_int64, c_double, c_int,
+                                           c_double, c_double, P, P]),
     "rmsf_qcp_batch": (c_int, [P, P, P, c_int64, P, P, P]),
     "rmsf_calc_rmsd_rotational_matrix": (c_int, [P, P, c_int64, P, P, POINTER(c_double)]),
     "rmsf_synth_frames": (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_uint64, P, P]),

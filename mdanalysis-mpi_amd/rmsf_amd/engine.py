@@ -734,6 +734,76 @@ class Engine:
              work.data_ptr(), need, self.stream)
         return label, core, k.value, rounds.value
 
+    def contact_counts_plan(self, n_a: int, n_b: int, n_frames: int, symmetric: bool = False):
+        """(tile_a, tile_b, frame_chunk, n_splits) of rmsf_contact_counts for
+        these sizes (rmsf_contact_counts_plan; host only)."""
+        v = [ctypes.c_int32(0) for _ in range(4)]
+        call("rmsf_contact_counts_plan", n_a, n_b, n_frames, int(bool(symmetric)), *(ctypes.byref(x) for x in v))
+        return tuple(x.value for x in v)
+
+    def _rows(self, rows):
+        """(host int32 array, its device copy) of a row-index array; (None,
+        None) for None, the dense rows."""
+        if rows is None:
+            return None, None
+        h = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        return h, torch.as_tensor(h).to(self.device)
+
+    def contact_counts(self, xyz_ptr: int, fstride: int, n_frames: int, n_atoms: int, rows_a, n_a: int, rows_b,
+                       n_b: int, radius: float, symmetric: bool = False, out: torch.Tensor | None = None):
+        """int32 [n_a, n_b] in HBM: the frames in which rows a_i and b_j of
+        the frames at xyz_ptr are in contact (rmsf_contact_counts,
+        csrc/contacts.hip).  ``rows_a`` / ``rows_b``: host index arrays into a
+        frame's n_atoms rows, None = rows 0..n-1; ``symmetric``: B is A and
+        ``rows_b`` / ``n_b`` are not used.  ``out``: an int32 tensor of at
+        least [n_a, n_b] with unit column stride to write into (columns at or
+        past n_b are left as they are).  Enqueued, not waited for."""
+        h_a, d_a = self._rows(rows_a)
+        if symmetric:
+            h_b, d_b, n_b = h_a, d_a, n_a
+        else:
+            h_b, d_b = self._rows(rows_b)
+        if (h_a is not None and h_a.size != n_a) or (h_b is not None and h_b.size != n_b):
+            raise ValueError("contact_counts: one row index per atom of a side is needed")
+        if out is None:
+            out = torch.empty((n_a, n_b), dtype=torch.int32, device=self.device)
+        elif (out.dtype != torch.int32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n_a
+              or out.shape[1] < n_b or out.stride(0) < n_b):
+            raise ValueError("contact_counts: buffer sizes")
+        need = int(self.lib.rmsf_contact_counts_workspace_bytes(n_a, n_b, n_frames, int(bool(symmetric))))
+        work = torch.empty(need // 8 + 1, dtype=torch.int64, device=self.device) if need else None
+        call("rmsf_contact_counts", xyz_ptr, fstride, n_frames, n_atoms, _ptr(d_a), None if h_a is None else
+             h_a.ctypes.data, n_a, _ptr(d_b), None if h_b is None else h_b.ctypes.data, n_b, int(bool(symmetric)),
+             float(radius), out.data_ptr(), out.stride(0), _ptr(work), need, self.stream)
+        return out[:n_a, :n_b]  # (the index copies are freed into the stream the kernels run on)
+
+    def contact_fraction(self, xyz_ptr: int, fstride: int, n_frames: int, n_atoms: int, rows, n_rows: int, pair_a,
+                         pair_b, r0, radius: float, method: int, beta: float = 5.0, lambda_constant: float = 1.8):
+        """(q f64 [n_frames], n_contacts int32 [n_frames]) in HBM over the
+        pairs (rows[pair_a[p]], rows[pair_b[p]]) of each frame
+        (rmsf_contact_fraction).  ``rows``: host indices into a frame's
+        n_atoms rows, None = rows 0..n_rows-1; ``pair_a`` / ``pair_b``: host
+        positions in ``rows``; ``r0``: f64 [P], read by soft_cut alone.
+        Enqueued, not waited for."""
+        h_rows, d_rows = self._rows(rows)
+        h_pa, d_pa = self._rows(pair_a)
+        h_pb, d_pb = self._rows(pair_b)
+        if h_pa.size != h_pb.size or (h_rows is not None and h_rows.size != n_rows):
+            raise ValueError("contact_fraction: buffer sizes")
+        d_r0 = None
+        if r0 is not None:
+            h_r0 = np.ascontiguousarray(r0, dtype=np.float64).reshape(-1)
+            if h_r0.size != h_pa.size:
+                raise ValueError("contact_fraction: one r0 per pair is needed")
+            d_r0 = torch.as_tensor(h_r0).to(self.device)
+        q = self.empty(n_frames)
+        n = torch.empty(n_frames, dtype=torch.int32, device=self.device)
+        call("rmsf_contact_fraction", xyz_ptr, fstride, n_frames, n_atoms, n_rows, _ptr(d_rows),
+             None if h_rows is None else h_rows.ctypes.data, d_pa.data_ptr(), d_pb.data_ptr(), h_pa.ctypes.data,
+             h_pb.ctypes.data, _ptr(d_r0), h_pa.size, float(radius), int(method), float(beta),
+             float(lambda_constant), q.data_ptr(), n.data_ptr(), self.stream)
+        return q, n
+
     def qcp_batch(self, A: torch.Tensor, E0: torch.Tensor, N: torch.Tensor):
         n = A.shape[0]
         rot = self.empty(n, 9)

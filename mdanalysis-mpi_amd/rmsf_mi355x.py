@@ -108,7 +108,27 @@ def main(argv=None) -> int:
                          "default every direction the covariance keeps)")
     ap.add_argument("--tica-lag", type=int, default=None, metavar="L",
                     help="--tica: the lag, in frames of the run's list")
+    ap.add_argument("--contact-map", default=None, metavar="OUT.npy",
+                    help="also write the contact counts of the selection against itself, int64 [n, n]: the frames in "
+                         "which two atoms are within --contact-radius of each other (rmsf_amd.ContactMap; no periodic "
+                         "images; one process only)")
+    ap.add_argument("--contacts", default=None, metavar="OUT.npy",
+                    help="also write the fraction of native contacts along the trajectory, f64 [F, 2] of frame and "
+                         "Q: the pairs within --contact-radius in the first frame (rmsf_amd.Contacts; one process "
+                         "only)")
+    ap.add_argument("--contact-radius", type=float, default=None, metavar="R",
+                    help="--contact-map / --contacts: the contact distance in A (default 4.5)")
+    ap.add_argument("--contacts-method", choices=["hard_cut", "radius_cut", "soft_cut"], default=None,
+                    help="--contacts: how a pair counts towards Q (default hard_cut)")
     a = ap.parse_args(argv)
+    if a.contact_radius is not None and not (a.contact_map or a.contacts):
+        ap.error("--contact-radius needs --contact-map or --contacts")
+    if a.contact_radius is not None and not 0.0 < a.contact_radius < float("inf"):
+        ap.error("--contact-radius must be positive and finite")
+    if a.contacts_method and not a.contacts:
+        ap.error(f"--contacts-method {a.contacts_method} needs --contacts")
+    if (a.contact_map or a.contacts) and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--contact-map and --contacts run in one process (no torch.distributed launch)")
     if bool(a.tica) != (a.tica_lag is not None):
         ap.error("--tica OUT.npz and --tica-lag L go together")
     if a.tica and a.tica_lag < 1:
@@ -283,6 +303,20 @@ def main(argv=None) -> int:
         print(f"PCA projection of {proj.shape[0]} frames on {proj.shape[1]} components: the first holds "
               f"{pca.results.cumulated_variance[0]:.4f} of the variance", flush=True)
         np.save(a.pca_transform, proj)
+    if a.contact_map or a.contacts:
+        from rmsf_amd import ContactMap, Contacts
+        ct_kw = {"select": dm_kw["select"]} if dm_kw else {}
+        radius = 4.5 if a.contact_radius is None else a.contact_radius
+        if a.contact_map:
+            cm = ContactMap(dm_input, radius=radius, **ct_kw).run().results
+            print(f"contact map at {radius} A over {cm.n_frames} frames: {cm.counts.shape[0]} atoms, "
+                  f"{int((cm.counts > 0).sum())} ordered pairs in contact in some frame", flush=True)
+            np.save(a.contact_map, cm.counts)
+        if a.contacts:
+            ct = Contacts(dm_input, radius=radius, method=a.contacts_method or "hard_cut", **ct_kw).run().results
+            print(f"native contacts at {radius} A: {len(ct.pairs)} pairs in the first frame, Q from "
+                  f"{ct.q.min():.4f} to {ct.q.max():.4f} over {ct.n_frames} frames", flush=True)
+            np.save(a.contacts, ct.timeseries)
     if a.tica:
         from rmsf_amd import TICA
         tica_kw = {"select": dm_kw["select"], "masses": dm_kw["weights"]} if dm_kw else {}
