@@ -955,7 +955,8 @@ int rmsf_cluster_dbscan_host(const double *h_m, int64_t n, int64_t ld,
  *   d2 = (dx*dx + dy*dy) + dz*dz with no FMA, d = sqrt(d2) correctly rounded,
  * and a pair is in contact iff d <= radius.  A NaN is never a contact, so an
  * atom with a non-finite coordinate in a frame loses its pairs in that frame
- * and nothing else changes.  No periodic images: the library reads no boxes.
+ * and nothing else changes.  No periodic images: these entries take no box
+ * (the rdf section below does).
  * rmsf_contact_threshold_sq(radius): the largest double t with sqrt(t) <=
  *   radius (NaN unless radius is positive and finite).  sqrt is monotone, so
  *   d2 <= t is the same predicate and the device entries take no root a pair.
@@ -1029,6 +1030,72 @@ int rmsf_contact_fraction_host(const float *h_xyz, int64_t frame_stride,
                                double radius, int method, double beta,
                                double lambda_constant, double *h_q,
                                int32_t *h_n_contacts);
+
+/* ---- radial distribution function: a histogram of pair distances, free or
+ * under the minimum image (csrc/rdf.hip, csrc/pair_image.h) ------------------
+ * One rule everywhere.  Coordinates are f32 as stored, no FMA anywhere;
+ *   dx = (double)xa - (double)xb, dy and dz likewise,
+ *   periodic: dx = dx - Lx * rint(dx * ix), ix = 1.0 / Lx formed once a frame
+ *     on the host; rint rounds half to even (numpy.rint's bits),
+ *   d2 = (dx*dx + dy*dy) + dz*dz, d = sqrt(d2) correctly rounded,
+ *   edges e_k = k * ((rmax - rmin) / nbins) + rmin for k < nbins, e_nbins = rmax
+ *     (numpy.linspace(rmin, rmax, nbins + 1)'s bits),
+ *   bin k iff e_k <= d < e_(k+1); the last bin also takes d == rmax; a NaN is
+ *     in no bin (numpy.histogram(d, bins=nbins, range=(rmin, rmax))'s counts).
+ * rmsf_rdf_edges: h_edges[nbins + 1] as above and h_thresholds_sq[nbins + 1],
+ *   the same predicate on d2 (either may be NULL; host only): T_k for k < nbins
+ *   is the smallest double whose correctly rounded root is >= e_k, T_nbins the
+ *   first double above the largest whose root is <= rmax, and bin k is
+ *   T_k <= d2 < T_(k+1).  The device compares d2 and takes no f64 root a pair.
+ * rmsf_rdf_counts: d_counts[k] (int64 [nbins]; nothing past nbins is written)
+ *   = the pairs (i, j, frame), i < n_a, j < n_b, whose distance is in bin k.
+ *   Frames, strides and index arrays as rmsf_contact_counts takes them.
+ *   symmetric != 0: A against itself (n_a == n_b, d_idx_a == d_idx_b): the
+ *   ordered pairs i != j; only tiles on or above the diagonal run, each
+ *   unordered pair adds 2, and the entry (i, i) is never counted.
+ *   excl_a, excl_b (0, 0: none): the pair (i, j) is skipped when i / excl_a ==
+ *   j / excl_b -- positions in the two sides, blocks of excl_a and excl_b of
+ *   them (upstream's exclusion_block); each must divide its side, and on the
+ *   symmetric route they are equal.
+ *   d_box / h_box (f64 [n_frames][6] = Lx, Ly, Lz, 1/Lx, 1/Ly, 1/Lz; the
+ *   device copy the kernel reads and the host copy the call checks; both NULL:
+ *   free space, with no image term compiled in).  Orthorhombic boxes only.
+ *   d_work: rmsf_rdf_counts_workspace_bytes(nbins) bytes, for the thresholds.
+ *   A workgroup owns a 64 x 64 tile of pairs and a run of frames staged
+ *   through LDS, and keeps int32 counters in LDS that it adds to the int64
+ *   bins by integer atomicAdd after one zeroing; a run of frames is short
+ *   enough that no int32 counter can wrap.  Integer sums: the same bytes
+ *   every run.  rmsf_rdf_counts_plan reports the tile's edges, the frame chunk
+ *   and the number of splits of the frames (host only).
+ * rmsf_rdf_counts_host: the definition in plain C++ on host pointers, a sqrt
+ *   a pair and a search of the edges; touches no device.
+ * RMSF_EINVAL before any launch: nbins outside 1..2048; rmin < 0, rmax <=
+ *   rmin or either non-finite; a box edge that is not positive and finite;
+ *   h_box[3 + k] != 1.0 / h_box[k]; rmax over half a box edge of any frame
+ *   (the minimum image is then not the only image in range); an index out of
+ *   range; symmetric with n_a != n_b; an exclusion block that does not divide
+ *   its side; a NULL or a size out of range.                                 */
+int rmsf_rdf_edges(double rmin, double rmax, int32_t nbins, double *h_edges,
+                   double *h_thresholds_sq);
+int rmsf_rdf_counts_plan(int64_t n_a, int64_t n_b, int64_t n_frames,
+                         int symmetric, int32_t *tile_a, int32_t *tile_b,
+                         int32_t *frame_chunk, int32_t *n_splits);
+size_t rmsf_rdf_counts_workspace_bytes(int32_t nbins);
+int rmsf_rdf_counts(const float *d_xyz, int64_t frame_stride, int64_t n_frames,
+                    int64_t n_atoms, const int32_t *d_idx_a,
+                    const int32_t *h_idx_a, int64_t n_a, const int32_t *d_idx_b,
+                    const int32_t *h_idx_b, int64_t n_b, int symmetric,
+                    int64_t excl_a, int64_t excl_b, const double *d_box,
+                    const double *h_box, double rmin, double rmax,
+                    int32_t nbins, int64_t *d_counts, void *d_work,
+                    size_t work_bytes, void *stream);
+int rmsf_rdf_counts_host(const float *h_xyz, int64_t frame_stride,
+                         int64_t n_frames, int64_t n_atoms,
+                         const int32_t *h_idx_a, int64_t n_a,
+                         const int32_t *h_idx_b, int64_t n_b, int symmetric,
+                         int64_t excl_a, int64_t excl_b, const double *h_box,
+                         double rmin, double rmax, int32_t nbins,
+                         int64_t *h_counts);
 
 /* ---- qcprot.CalcRMSDRotationalMatrix (RMSF.py:48) --------------------------
  * Batched QCP on device: A[n][9], E0[n], atom counts N[n] -> rot[n][9],
@@ -1146,6 +1213,8 @@ int rmsf_xtc_open(const char *path, rmsf_xtc **out, int64_t *n_atoms,
 int rmsf_xtc_close(rmsf_xtc *x);
 int rmsf_xtc_frame_info(const rmsf_xtc *x, int64_t frame, int32_t *step,
                         float *time, float *box9);
+/* Every frame's box as the file holds it: h_box9[n_frames][9], nm.          */
+int rmsf_xtc_boxes(const rmsf_xtc *x, float *h_box9);
 /* Decode frames f0, f0+step, ... (n) into h_out[n][rows][3] (rows = n_sel
  * when h_sel != NULL, else n_atoms), frame-parallel on n_threads threads. */
 int rmsf_xtc_read(const rmsf_xtc *x, int64_t f0, int64_t n, int64_t step,

@@ -629,6 +629,12 @@ RMSF_EXPORT int rmsf_xtc_frame_info(const rmsf_xtc *x, int64_t f, int32_t *step,
   return RMSF_OK;
 }
 
+RMSF_EXPORT int rmsf_xtc_boxes(const rmsf_xtc *x, float *h_box9) {
+  if (!x || !h_box9) return fail(RMSF_EINVAL, "rmsf_xtc_boxes: bad arguments");
+  if (!x->box.empty()) std::memcpy(h_box9, x->box.data(), x->box.size() * sizeof(float));
+  return RMSF_OK;
+}
+
 RMSF_EXPORT int rmsf_xtc_frame_record(const rmsf_xtc *x, int64_t f, int64_t *offset, int64_t *bytes) {
   if (!x || f < 0 || f >= (int64_t)x->offset.size()) return fail(RMSF_EINVAL, "rmsf_xtc_frame_record: bad frame");
   if (offset) *offset = x->offset[f];

@@ -36,6 +36,10 @@ Public surface (mirrors the reference's names):
     contacts Q(t), named as MDAnalysis.analysis.contacts.Contacts names it, and the count of frames in
     which each pair of two selections touches; ``contact_threshold_sq`` is the squared cutoff the device
     compares against.  No periodic boundary conditions
+  * ``InterRDF`` -- the radial distribution function g(r) of two selections, named as
+    MDAnalysis.analysis.rdf.InterRDF names it, free or under the minimum image of per-frame orthorhombic
+    boxes (arrays, or an ``.xtc`` file's own): ``InterRDF(traj, box=(30, 30, 30)).run().results.rdf``;
+    ``rdf_edges`` gives the bin edges and the squared thresholds the device compares against
 """
 from ._lib import RmsfEmptyError, RmsfError, load as load_library
 from .parallel import blocks
@@ -48,8 +52,11 @@ from .distances import CrossDistanceMatrix, DiffusionMap, DistanceMatrix, discre
 from .clustering import DBSCAN, Cluster
 from .tica import TICA, tica_from_comoments
 from .contacts import ContactMap, Contacts, contact_threshold_sq
+from .rdf import InterRDF, rdf_edges
 
 __all__ = [
+    "InterRDF",
+    "rdf_edges",
     "ContactMap",
     "Contacts",
     "contact_threshold_sq",

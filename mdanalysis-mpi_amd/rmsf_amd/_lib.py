@@ -157,6 +157,14 @@ SIGNATURES = {
                                       c_int, c_double, c_double, P, P, P]),
     "rmsf_contact_fraction_host": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, P, P, c_int64, c_double, c_int,
                                            c_double, c_double, P, P]),
+    "rmsf_rdf_edges": (c_int, [c_double, c_double, c_int32, P, P]),
+    "rmsf_rdf_counts_plan": (c_int, [c_int64, c_int64, c_int64, c_int, POINTER(c_int32), POINTER(c_int32),
+                                     POINTER(c_int32), POINTER(c_int32)]),
+    "rmsf_rdf_counts_workspace_bytes": (c_size_t, [c_int32]),
+    "rmsf_rdf_counts": (c_int, [P, c_int64, c_int64, c_int64, P, P, c_int64, P, P, c_int64, c_int, c_int64, c_int64, P,
+                                P, c_double, c_double, c_int32, P, P, c_size_t, P]),
+    "rmsf_rdf_counts_host": (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, c_int, c_int64, c_int64, P,
+                                     c_double, c_double, c_int32, P]),
     "rmsf_qcp_batch": (c_int, [P, P, P, c_int64, P, P, P]),
     "rmsf_calc_rmsd_rotational_matrix": (c_int, [P, P, c_int64, P, P, POINTER(c_double)]),
     "rmsf_synth_frames": (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_uint64, P, P]),
@@ -175,6 +183,7 @@ SIGNATURES = {
     "rmsf_xtc_open": (c_int, [c_char_p, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64)]),
     "rmsf_xtc_close": (c_int, [P]),
     "rmsf_xtc_frame_info": (c_int, [P, c_int64, POINTER(c_int32), POINTER(ctypes.c_float), P]),
+    "rmsf_xtc_boxes": (c_int, [P, P]),
     "rmsf_xtc_read": (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, P, c_int]),
     "rmsf_xtc_write": (c_int, [c_char_p, P, c_int64, c_int64, ctypes.c_float, P, c_int]),
     "rmsf_xtc_frame_record": (c_int, [P, c_int64, POINTER(c_int64), POINTER(c_int64)]),

@@ -11,8 +11,9 @@ never a contact: an atom with a non-finite coordinate in a frame loses its
 pairs in that frame and nothing else changes.  numpy evaluates the same
 expression to the same bits, so counts are compared with it for equality.
 
-No periodic boundary conditions are applied: the library reads no boxes, and
-a pair across a periodic image is as far apart as its stored coordinates say.
+No periodic boundary conditions are applied: these classes take no box (only
+``InterRDF`` does), and a pair across a periodic image is as far apart as its
+stored coordinates say.
 
 Contacts are invariant under superposition, so nothing is aligned.  Nothing of
 the size [F, n, n] is ever formed: the count kernel keeps a tile of integer
@@ -194,8 +195,8 @@ class ContactMap(_PairAnalysis):
     j of ``select_b`` are within ``radius`` of each other, and
     ``results.frequency = counts / n_frames``.  The rule is the module's: f64
     differences of the f32 coordinates, ``d <= radius``, a NaN never a
-    contact.  No periodic boundary conditions are applied -- the library reads
-    no boxes.
+    contact.  No periodic boundary conditions are applied -- there is no
+    ``box=`` here yet.
 
     Parameters
     ----------
@@ -273,7 +274,7 @@ class Contacts(_PairAnalysis):
           a native pair with a non-finite coordinate in a frame has a NaN
           term and makes that frame's soft q NaN, as numpy's would be.
 
-    No periodic boundary conditions are applied -- the library reads no boxes.
+    No periodic boundary conditions are applied -- there is no ``box=`` here yet.
 
     Parameters
     ----------

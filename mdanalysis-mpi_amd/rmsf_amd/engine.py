@@ -804,6 +804,52 @@ class Engine:
              float(lambda_constant), q.data_ptr(), n.data_ptr(), self.stream)
         return q, n
 
+    def rdf_counts_plan(self, n_a: int, n_b: int, n_frames: int, symmetric: bool = False):
+        """(tile_a, tile_b, frame_chunk, n_splits) of rmsf_rdf_counts for these
+        sizes (rmsf_rdf_counts_plan; host only)."""
+        v = [ctypes.c_int32(0) for _ in range(4)]
+        call("rmsf_rdf_counts_plan", n_a, n_b, n_frames, int(bool(symmetric)), *(ctypes.byref(x) for x in v))
+        return tuple(x.value for x in v)
+
+    def rdf_counts(self, xyz_ptr: int, fstride: int, n_frames: int, n_atoms: int, rows_a, n_a: int, rows_b, n_b: int,
+                   rmin: float, rmax: float, nbins: int, symmetric: bool = False, exclusion_block=None, box=None,
+                   out: torch.Tensor | None = None):
+        """int64 [nbins] in HBM: the histogram of the distances of rows a_i and
+        b_j of the frames at xyz_ptr (rmsf_rdf_counts, csrc/rdf.hip).
+        ``rows_a`` / ``rows_b`` / ``symmetric`` as ``contact_counts``;
+        ``exclusion_block``: (excl_a, excl_b) or None; ``box``: host f64
+        [n_frames, 3] of box edges, None for free space; ``out``: a contiguous
+        int64 tensor of at least nbins to write into (entries at or past nbins
+        are left as they are).  Enqueued, not waited for."""
+        h_a, d_a = self._rows(rows_a)
+        if symmetric:
+            h_b, d_b, n_b = h_a, d_a, n_a
+        else:
+            h_b, d_b = self._rows(rows_b)
+        if (h_a is not None and h_a.size != n_a) or (h_b is not None and h_b.size != n_b):
+            raise ValueError("rdf_counts: one row index per atom of a side is needed")
+        ea, eb = (0, 0) if exclusion_block is None else (int(exclusion_block[0]), int(exclusion_block[1]))
+        h_box = d_box = None
+        if box is not None:
+            edge = np.ascontiguousarray(box, dtype=np.float64)
+            if edge.shape != (n_frames, 3):
+                raise ValueError(f"rdf_counts: box must be [n_frames, 3], got {edge.shape}")
+            with np.errstate(divide="ignore", invalid="ignore"):
+                h_box = np.ascontiguousarray(np.concatenate([edge, 1.0 / edge], axis=1))
+            d_box = torch.as_tensor(h_box).to(self.device)
+        nbins = int(nbins)
+        if out is None:
+            out = torch.empty(max(nbins, 1), dtype=torch.int64, device=self.device)
+        elif out.dtype != torch.int64 or out.dim() != 1 or not out.is_contiguous() or out.shape[0] < nbins:
+            raise ValueError("rdf_counts: buffer sizes")
+        need = int(self.lib.rmsf_rdf_counts_workspace_bytes(nbins))
+        work = torch.empty(need // 8 + 1, dtype=torch.int64, device=self.device)
+        call("rmsf_rdf_counts", xyz_ptr, fstride, n_frames, n_atoms, _ptr(d_a), None if h_a is None else
+             h_a.ctypes.data, n_a, _ptr(d_b), None if h_b is None else h_b.ctypes.data, n_b, int(bool(symmetric)),
+             ea, eb, _ptr(d_box), None if h_box is None else h_box.ctypes.data, float(rmin), float(rmax), nbins,
+             out.data_ptr(), work.data_ptr(), need, self.stream)
+        return out[:nbins]  # (the index, box and workspace copies are freed into the stream the kernel runs on)
+
     def qcp_batch(self, A: torch.Tensor, E0: torch.Tensor, N: torch.Tensor):
         n = A.shape[0]
         rot = self.empty(n, 9)

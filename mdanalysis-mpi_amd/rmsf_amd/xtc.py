@@ -47,6 +47,25 @@ class XTCFile:
         call("rmsf_xtc_frame_info", self._h, f, ctypes.byref(st), ctypes.byref(tm), box.ctypes.data)
         return st.value, tm.value, box.reshape(3, 3)
 
+    def boxes(self) -> np.ndarray:
+        """f64 [n_frames, 3]: every frame's box edges in Angstrom -- the
+        file's f32 nm diagonal, widened to f64, then ``* 10.0``.  Only
+        orthorhombic boxes: a nonzero off-diagonal entry in any frame is
+        NotImplementedError; a frame whose box is all zeros (a file written
+        without one) is ValueError.  ``frame_info`` still returns a frame's
+        box as the file holds it."""
+        raw = np.empty((self.n_frames, 9), dtype=np.float32)
+        call("rmsf_xtc_boxes", self._h, raw.ctypes.data)
+        off = np.delete(raw, [0, 4, 8], axis=1)
+        if (off != 0).any():
+            f = int(np.nonzero((off != 0).any(axis=1))[0][0])
+            raise NotImplementedError(f"{self.path}: frame {f} has a triclinic box (nonzero off-diagonal entries); "
+                                      "only orthorhombic boxes are supported")
+        empty = (raw == 0).all(axis=1)
+        if empty.any():
+            raise ValueError(f"{self.path}: frame {int(np.nonzero(empty)[0][0])} has no box (all zeros)")
+        return raw[:, [0, 4, 8]].astype(np.float64) * 10.0
+
     def record(self, f: int) -> tuple[int, int]:
         """(byte offset, byte length) of frame f's XDR record in the file."""
         off, n = ctypes.c_int64(), ctypes.c_int64()

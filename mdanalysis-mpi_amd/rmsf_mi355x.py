@@ -120,7 +120,46 @@ def main(argv=None) -> int:
                     help="--contact-map / --contacts: the contact distance in A (default 4.5)")
     ap.add_argument("--contacts-method", choices=["hard_cut", "radius_cut", "soft_cut"], default=None,
                     help="--contacts: how a pair counts towards Q (default hard_cut)")
+    ap.add_argument("--rdf", default=None, metavar="OUT.npz",
+                    help="also write the radial distribution function of the selection against itself (or against "
+                         "--rdf-select-b): bins, edges, count and rdf (rmsf_amd.InterRDF; one process only).  "
+                         "Without --rdf-box the run is in free space and rdf is the density-normalised count")
+    ap.add_argument("--rdf-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="--rdf: the range of distances in A (default 0 15)")
+    ap.add_argument("--rdf-nbins", type=int, default=None, metavar="N", help="--rdf: the number of bins (default 75)")
+    ap.add_argument("--rdf-box", nargs="+", default=None, metavar="file|LX LY LZ",
+                    help="--rdf: 'file' for the boxes of an .xtc trajectory, or three edges in A of one orthorhombic "
+                         "box; distances then follow the minimum image and rdf is normalised by the volume")
+    ap.add_argument("--rdf-select-b", default=None, metavar="SEL",
+                    help="--rdf: the second group, a selection string read as --select is (natively read "
+                         "topologies only)")
     a = ap.parse_args(argv)
+    rdf_box = None
+    if not a.rdf and (a.rdf_range or a.rdf_nbins is not None or a.rdf_box or a.rdf_select_b):
+        ap.error("--rdf-range, --rdf-nbins, --rdf-box and --rdf-select-b need --rdf OUT.npz")
+    if a.rdf:
+        if int(os.environ.get("WORLD_SIZE", 1)) > 1:
+            ap.error("--rdf runs in one process (no torch.distributed launch)")
+        lo, hi = a.rdf_range or (0.0, 15.0)
+        if not 0.0 <= lo < hi < float("inf"):
+            ap.error("--rdf-range needs 0 <= LO < HI, both finite")
+        if a.rdf_nbins is not None and not 1 <= a.rdf_nbins <= 2048:
+            ap.error("--rdf-nbins must be in 1..2048")
+        if a.rdf_box == ["file"]:
+            if not (a.trajectory and a.trajectory.lower().endswith(".xtc")):
+                ap.error("--rdf-box file needs an .xtc --trajectory")
+            rdf_box = "file"
+        elif a.rdf_box is not None:
+            try:
+                rdf_box = [float(v) for v in a.rdf_box]
+            except ValueError:
+                rdf_box = []
+            if len(rdf_box) != 3 or not all(0.0 < v < float("inf") for v in rdf_box):
+                ap.error("--rdf-box takes 'file' or three positive finite edges LX LY LZ")
+            if hi > 0.5 * min(rdf_box):
+                ap.error("--rdf-range ends over half the shortest --rdf-box edge")
+        if a.rdf_select_b and a.synthetic:
+            ap.error("--rdf-select-b needs a topology")
     if a.contact_radius is not None and not (a.contact_map or a.contacts):
         ap.error("--contact-radius needs --contact-map or --contacts")
     if a.contact_radius is not None and not 0.0 < a.contact_radius < float("inf"):
@@ -202,6 +241,7 @@ def main(argv=None) -> int:
     cov = None
     dm_input, dm_kw = None, {}   # what --dist-matrix reads: the RMSF run's own input
     cross_b = None               # what --cross-with names, read as the input is
+    rdf_sel_b = None             # what --rdf-select-b selects
     if a.synthetic:
         n_atoms, n_frames = a.synthetic
         eng = Engine()
@@ -253,6 +293,8 @@ def main(argv=None) -> int:
                            merge_order=a.merge_order, **cov_kw).run().results
             rmsf, cov = results.rmsf, (results.covariance if a.covariance else None)
             dm_input, dm_kw = traj, {"select": sel, "weights": masses}
+            if a.rdf_select_b:
+                rdf_sel_b = top.select(a.rdf_select_b)
             if a.cross_with:
                 cross_b = (a.cross_with if a.cross_with.lower().endswith((".xtc", ".dcd"))
                            else GroTopology(a.cross_with).frames)
@@ -317,6 +359,20 @@ def main(argv=None) -> int:
             print(f"native contacts at {radius} A: {len(ct.pairs)} pairs in the first frame, Q from "
                   f"{ct.q.min():.4f} to {ct.q.max():.4f} over {ct.n_frames} frames", flush=True)
             np.save(a.contacts, ct.timeseries)
+    if a.rdf:
+        from rmsf_amd import InterRDF
+        if a.rdf_select_b and rdf_sel_b is None:
+            raise SystemExit("--rdf-select-b is read through the native topology reader only (no MDAnalysis group)")
+        rdf_kw = {"select": dm_kw["select"]} if dm_kw else {}
+        if rdf_box == "file" and not isinstance(dm_input, str):
+            raise SystemExit("--rdf-box file reads the boxes through the native .xtc reader only")
+        rd = InterRDF(dm_input, select_b=rdf_sel_b, nbins=75 if a.rdf_nbins is None else a.rdf_nbins,
+                      range=tuple(a.rdf_range or (0.0, 15.0)), norm="density" if rdf_box is None else "rdf",
+                      box=rdf_box, **rdf_kw).run().results
+        print(f"radial distribution function over {rd.n_frames} frames, {len(rd.bins)} bins on "
+              f"[{rd.edges[0]}, {rd.edges[-1]}] A: {int(rd.count_int.sum())} pair distances in range, the largest "
+              f"value {np.nanmax(rd.rdf):.4f} at {rd.bins[int(np.nanargmax(rd.rdf))]:.3f} A", flush=True)
+        np.savez(a.rdf, bins=rd.bins, edges=rd.edges, count=rd.count, rdf=rd.rdf, volume=rd.volume)
     if a.tica:
         from rmsf_amd import TICA
         tica_kw = {"select": dm_kw["select"], "masses": dm_kw["weights"]} if dm_kw else {}
