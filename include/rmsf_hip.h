@@ -1097,6 +1097,80 @@ int rmsf_rdf_counts_host(const float *h_xyz, int64_t frame_stride,
                          double rmin, double rmax, int32_t nbins,
                          int64_t *h_counts);
 
+/* ---- mean squared displacement: every atom at every lag, with the "nojump"
+ * unwrap (csrc/msd.hip, csrc/pair_image.h) ------------------------------------
+ * One rule everywhere, host and device, all f64, no FMA anywhere.  Frames are
+ * positions k = 0..F-1 of the run; a lag counts positions.
+ *   coordinates: f32 as stored, widened: (double)x_c(k);
+ *   free:    u_c(k) = (double)x_c(k);
+ *   nojump:  u_c(0) = (double)x_c(0),
+ *            u_c(k) = u_c(k-1) + image((double)x_c(k) - (double)x_c(k-1)),
+ *            image(d) = d - L_c(k) * rint(d * i_c(k)) with the box of frame k,
+ *            i = 1.0 / L formed on the host, rint half to even (numpy.rint's
+ *            bits): one in-order add chain an atom-coordinate, all three
+ *            coordinates whatever the mask.  A non-finite coordinate at frame
+ *            k makes that chain NaN from k on and touches nothing else;
+ *   term:    d(a,t,tau) = (dx*dx + dy*dy) + dz*dz, dc = u_c(t+tau) - u_c(t);
+ *            dims_mask (bit 0 x, bit 1 y, bit 2 z; 1..7) names the
+ *            coordinates, the others are left out of the expression (not
+ *            multiplied by zero): dx*dx + dz*dz, dy*dy, ...;
+ *   sum:     S(a,tau) = sum over t = 0..F-tau-1 of d(a,t,tau), in a fixed
+ *            order of the kernel's choosing, no float atomics, the same bytes
+ *            every run; msd(a,tau) = S(a,tau) / (double)(F - tau), one
+ *            division.  The terms are not negative, so any order of the N =
+ *            F - tau terms is within (N - 1) 2^-53 relative of the exact sum
+ *            and msd within (N + 8) 2^-53 of the exact quotient; msd(a,0) is
+ *            0.0 exactly for a finite atom;
+ *   mean:    mean(tau) = (sum over a of msd(a,tau)) / (double)n_sel, summed in
+ *            a fixed order, within (n_sel + 8) 2^-53 relative of the exact
+ *            mean of the values summed; a NaN propagates;
+ *   lags:    tau = 0..n_lags-1, 1 <= n_lags <= F.
+ * rmsf_msd_plane_ld(n_frames): the leading dimension the planes should have
+ *   (>= n_frames; 0 for a size out of range).
+ * rmsf_msd_planes: d_planes (f64 [n_sel][3][ld], ld >= n_frames) = u_c(k) of
+ *   the rows d_idx names (frames, strides and the index array as
+ *   rmsf_contact_counts takes them), atom-major from frame-major rows through
+ *   an LDS transpose.  d_box / h_box (f64 [n_frames][6] = Lx, Ly, Lz, 1/Lx,
+ *   1/Ly, 1/Lz; the device copy the kernel reads and the host copy the call
+ *   checks): nojump; both NULL: free.  Columns n_frames..ld-1 are written 0.0
+ *   and nothing past [n_sel][3][ld] is written.
+ * rmsf_msd_lags: d_msd (f64 [n_lags][ld_out], ld_out >= n_sel; columns at or
+ *   past n_sel are not written) = msd(a,tau), and d_mean (f64 [n_lags], or
+ *   NULL to skip it) = mean(tau).  A workgroup owns an atom, a block of lags
+ *   and a run of origins staged through LDS; where atoms times lag blocks are
+ *   few the origins are split across workgroups, the partial sums go through
+ *   d_work (rmsf_msd_workspace_bytes; 0 with no split, d_work may then be
+ *   NULL) and a second launch adds them in split order.  rmsf_msd_plan reports
+ *   what the launcher chooses: the lags a workgroup, the origins staged at a
+ *   time and the number of splits (host only).
+ * The _host entries are the definition in plain C++ on host pointers, summed
+ * in order of t (the mean in order of a), and touch no device.
+ * RMSF_EINVAL before any launch: n_lags outside 1..n_frames; a mask outside
+ *   1..7; a box edge that is not positive and finite; h_box[3 + k] != 1.0 /
+ *   h_box[k]; exactly one of d_box / h_box NULL; an index out of range; ld <
+ *   n_frames; ld_out < n_sel; a workspace too small; a NULL or a size out of
+ *   range (frames up to 4,194,240, rows up to INT32_MAX / 3).               */
+int64_t rmsf_msd_plane_ld(int64_t n_frames);
+int rmsf_msd_plan(int64_t n_sel, int64_t n_frames, int64_t n_lags,
+                  int32_t *lag_block, int32_t *origin_chunk, int32_t *n_splits);
+size_t rmsf_msd_workspace_bytes(int64_t n_sel, int64_t n_frames,
+                                int64_t n_lags);
+int rmsf_msd_planes(const float *d_xyz, int64_t frame_stride, int64_t n_frames,
+                    int64_t n_atoms, const int32_t *d_idx, const int32_t *h_idx,
+                    int64_t n_sel, const double *d_box, const double *h_box,
+                    double *d_planes, int64_t ld, void *stream);
+int rmsf_msd_lags(const double *d_planes, int64_t ld, int64_t n_sel,
+                  int64_t n_frames, int64_t n_lags, int dims_mask,
+                  double *d_msd, int64_t ld_out, double *d_mean, void *d_work,
+                  size_t work_bytes, void *stream);
+int rmsf_msd_planes_host(const float *h_xyz, int64_t frame_stride,
+                         int64_t n_frames, int64_t n_atoms,
+                         const int32_t *h_idx, int64_t n_sel,
+                         const double *h_box, double *h_planes, int64_t ld);
+int rmsf_msd_lags_host(const double *h_planes, int64_t ld, int64_t n_sel,
+                       int64_t n_frames, int64_t n_lags, int dims_mask,
+                       double *h_msd, int64_t ld_out, double *h_mean);
+
 /* ---- qcprot.CalcRMSDRotationalMatrix (RMSF.py:48) --------------------------
  * Batched QCP on device: A[n][9], E0[n], atom counts N[n] -> rot[n][9],
  * rmsd[n].  Exposed for the upstream known-answer test.                      */

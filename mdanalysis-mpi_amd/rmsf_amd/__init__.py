@@ -40,6 +40,11 @@ Public surface (mirrors the reference's names):
     MDAnalysis.analysis.rdf.InterRDF names it, free or under the minimum image of per-frame orthorhombic
     boxes (arrays, or an ``.xtc`` file's own): ``InterRDF(traj, box=(30, 30, 30)).run().results.rdf``;
     ``rdf_edges`` gives the bin edges and the squared thresholds the device compares against
+  * ``EinsteinMSD`` -- the mean squared displacement of every atom at every lag and its mean over the
+    atoms, named as MDAnalysis.analysis.msd.EinsteinMSD names it, by the windowed sum on the f64 vector
+    units, with the "nojump" unwrap of a wrapped trajectory under per-frame orthorhombic boxes:
+    ``EinsteinMSD(traj, unwrap="nojump", box="file").run().results.timeseries``;
+    ``diffusion_coefficient`` fits the slope
 """
 from ._lib import RmsfEmptyError, RmsfError, load as load_library
 from .parallel import blocks
@@ -53,8 +58,10 @@ from .clustering import DBSCAN, Cluster
 from .tica import TICA, tica_from_comoments
 from .contacts import ContactMap, Contacts, contact_threshold_sq
 from .rdf import InterRDF, rdf_edges
+from .msd import EinsteinMSD
 
 __all__ = [
+    "EinsteinMSD",
     "InterRDF",
     "rdf_edges",
     "ContactMap",

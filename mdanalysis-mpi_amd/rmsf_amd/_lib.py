@@ -165,6 +165,13 @@ SIGNATURES = {
                                 P, c_double, c_double, c_int32, P, P, c_size_t, P]),
     "rmsf_rdf_counts_host": (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, c_int, c_int64, c_int64, P,
                                      c_double, c_double, c_int32, P]),
+    "rmsf_msd_plane_ld": (c_int64, [c_int64]),
+    "rmsf_msd_plan": (c_int, [c_int64, c_int64, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "rmsf_msd_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "rmsf_msd_planes": (c_int, [P, c_int64, c_int64, c_int64, P, P, c_int64, P, P, P, c_int64, P]),
+    "rmsf_msd_lags": (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_int, P, c_int64, P, P, c_size_t, P]),
+    "rmsf_msd_planes_host": (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, P, P, c_int64]),
+    "rmsf_msd_lags_host": (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_int, P, c_int64, P]),
     "rmsf_qcp_batch": (c_int, [P, P, P, c_int64, P, P, P]),
     "rmsf_calc_rmsd_rotational_matrix": (c_int, [P, P, c_int64, P, P, POINTER(c_double)]),
     "rmsf_synth_frames": (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_uint64, P, P]),

@@ -123,7 +123,7 @@ class _PairAnalysis:
         if layout not in ("fac", "soa"):
             raise ValueError(f"layout must be 'fac' or 'soa', got {layout!r}")
         self._input = traj
-        self.radius = _check_radius(radius)
+        self.radius = None if radius is None else _check_radius(radius)  # (None: an analysis with no distance)
         self.select = _selection(select, "select")
         self.select_b = _selection(select_b, "select_b")
         self.symmetric = select_b is None

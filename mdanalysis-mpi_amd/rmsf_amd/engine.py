@@ -850,6 +850,85 @@ class Engine:
              out.data_ptr(), work.data_ptr(), need, self.stream)
         return out[:nbins]  # (the index, box and workspace copies are freed into the stream the kernel runs on)
 
+    def msd_plane_ld(self, n_frames: int) -> int:
+        """The leading dimension ``msd_planes`` gives its planes
+        (rmsf_msd_plane_ld; host only)."""
+        ld = int(self.lib.rmsf_msd_plane_ld(int(n_frames)))
+        if ld < 1:
+            raise ValueError(f"msd_plane_ld: {n_frames} frames are out of range")
+        return ld
+
+    def msd_plan(self, n_sel: int, n_frames: int, n_lags: int):
+        """(lag_block, origin_chunk, n_splits) of rmsf_msd_lags for these
+        sizes (rmsf_msd_plan; host only)."""
+        v = [ctypes.c_int32(0) for _ in range(3)]
+        call("rmsf_msd_plan", n_sel, n_frames, n_lags, *(ctypes.byref(x) for x in v))
+        return tuple(x.value for x in v)
+
+    def msd_planes(self, xyz_ptr: int, fstride: int, n_frames: int, n_atoms: int, rows, n_sel: int, box=None,
+                   out: torch.Tensor | None = None):
+        """f64 [n_sel, 3, ld] in HBM, of which [:, :, :n_frames] is returned:
+        the coordinates of the rows ``rows`` (host indices into a frame's
+        n_atoms rows, None = rows 0..n_sel-1) of the frames at xyz_ptr,
+        widened and atom-major, unwrapped by the nojump rule where ``box``
+        (host f64 [n_frames, 3] of box edges) is given (rmsf_msd_planes,
+        csrc/msd.hip).  ``out``: a contiguous f64 tensor [>= n_sel, 3, ld >=
+        n_frames] to write into; columns n_frames..ld-1 are zeroed.  Enqueued,
+        not waited for."""
+        h_idx, d_idx = self._rows(rows)
+        if h_idx is not None and h_idx.size != n_sel:
+            raise ValueError("msd_planes: one row index per atom is needed")
+        h_box = d_box = None
+        if box is not None:
+            edge = np.ascontiguousarray(box, dtype=np.float64)
+            if edge.shape != (n_frames, 3):
+                raise ValueError(f"msd_planes: box must be [n_frames, 3], got {edge.shape}")
+            with np.errstate(divide="ignore", invalid="ignore"):
+                h_box = np.ascontiguousarray(np.concatenate([edge, 1.0 / edge], axis=1))
+            d_box = torch.as_tensor(h_box).to(self.device)
+        if out is None:
+            out = self.empty(n_sel, 3, self.msd_plane_ld(n_frames))
+        elif (out.dtype != F64 or out.dim() != 3 or not out.is_contiguous() or out.shape[0] < n_sel
+              or out.shape[1] != 3 or out.shape[2] < n_frames):
+            raise ValueError("msd_planes: buffer sizes")
+        call("rmsf_msd_planes", xyz_ptr, fstride, n_frames, n_atoms, _ptr(d_idx), None if h_idx is None else
+             h_idx.ctypes.data, n_sel, _ptr(d_box), None if h_box is None else h_box.ctypes.data, out.data_ptr(),
+             out.shape[2], self.stream)
+        return out[:n_sel, :, :n_frames]  # (the index and box copies are freed into the stream the kernel runs on)
+
+    def msd_lags(self, planes: torch.Tensor, n_frames: int, n_lags: int, dims_mask: int = 7,
+                 out: torch.Tensor | None = None, mean: torch.Tensor | bool = True):
+        """(msd f64 [n_lags, n_sel], mean f64 [n_lags] or None) in HBM from
+        ``msd_planes``' planes [n_sel, 3, >= n_frames] (unit stride along the
+        frames): the mean squared displacement of every atom at the lags
+        0..n_lags-1 over the coordinates ``dims_mask`` names (bit 0 x, 1 y, 2
+        z) and its mean over the atoms (rmsf_msd_lags).  ``out``: an f64
+        tensor of at least [n_lags, n_sel] with unit column stride to write
+        into (entries past either bound are left as they are); ``mean``: a
+        contiguous f64 tensor of at least n_lags to write into, True to
+        allocate one, False to skip the mean.  Enqueued, not waited for."""
+        if (planes.dtype != F64 or planes.dim() != 3 or planes.shape[1] != 3 or planes.stride(2) != 1
+                or planes.shape[2] < n_frames or planes.stride(1) < n_frames
+                or planes.stride(0) != 3 * planes.stride(1)):
+            raise ValueError("msd_lags: planes must be f64 [n_sel, 3, ld >= n_frames], rows ld apart")
+        n_sel, n_lags = planes.shape[0], int(n_lags)
+        if out is None:
+            out = self.empty(max(n_lags, 1), n_sel)
+        elif (out.dtype != F64 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n_lags
+              or out.shape[1] < n_sel or out.stride(0) < n_sel):
+            raise ValueError("msd_lags: buffer sizes")
+        if mean is True:
+            mean = self.empty(max(n_lags, 1))
+        elif mean is False or mean is None:
+            mean = None
+        elif mean.dtype != F64 or mean.dim() != 1 or not mean.is_contiguous() or mean.shape[0] < n_lags:
+            raise ValueError("msd_lags: buffer sizes")
+        need = int(self.lib.rmsf_msd_workspace_bytes(n_sel, n_frames, n_lags))
+        work = torch.empty(need // 8, dtype=F64, device=self.device) if need else None
+        call("rmsf_msd_lags", planes.data_ptr(), planes.stride(1), n_sel, n_frames, n_lags, int(dims_mask),
+             out.data_ptr(), out.stride(0), _ptr(mean), _ptr(work), need, self.stream)
+        return out[:n_lags, :n_sel], None if mean is None else mean[:n_lags]
+
     def qcp_batch(self, A: torch.Tensor, E0: torch.Tensor, N: torch.Tensor):
         n = A.shape[0]
         rot = self.empty(n, 9)

@@ -80,6 +80,36 @@ def _box_edges(box, what: str) -> np.ndarray:
     return np.ascontiguousarray(b)
 
 
+def _box_argument(box, traj):
+    """A ``box=`` argument checked: None, ``"file"`` (``traj`` must be an
+    ``.xtc`` path) or the edges f64 [3] / [n_traj, 3]."""
+    if isinstance(box, str):
+        if box != "file":
+            raise ValueError(f"box must be None, an array or 'file', got {box!r}")
+        is_path = isinstance(traj, (str, bytes)) or hasattr(traj, "__fspath__")
+        if not (is_path and str(os.fspath(traj)).lower().endswith(".xtc")):
+            raise ValueError("box='file' reads the boxes of an .xtc path; pass the boxes as an array for any "
+                             "other input")
+        return box
+    return None if box is None else _box_edges(box, "box")
+
+
+def _run_boxes(box, traj, n_traj: int, frames: np.ndarray):
+    """f64 [len(frames), 3] for the run's frames from a checked ``box=``
+    argument; None in free space."""
+    if box is None:
+        return None
+    if isinstance(box, str):
+        from .xtc import XTCFile
+        with XTCFile(os.fspath(traj)) as fh:
+            box = fh.boxes()
+    if box.ndim == 1:
+        return np.broadcast_to(box, (len(frames), 3)).copy()
+    if box.shape[0] != n_traj:
+        raise ValueError(f"box has {box.shape[0]} rows, the trajectory {n_traj} frames")
+    return np.ascontiguousarray(box[frames])
+
+
 class InterRDF(_PairAnalysis):
     """The radial distribution function of ``select_b`` around ``select``,
     mirroring ``MDAnalysis.analysis.rdf.InterRDF`` (restated, not verified).
@@ -139,36 +169,19 @@ class InterRDF(_PairAnalysis):
                 raise ValueError(f"exclusion_block must be positive, got {exclusion_block!r}")
             exclusion_block = (ea, eb)
         self.exclusion_block = exclusion_block
-        if isinstance(box, str):
-            if box != "file":
-                raise ValueError(f"box must be None, an array or 'file', got {box!r}")
-            is_path = isinstance(traj, (str, bytes)) or hasattr(traj, "__fspath__")
-            if not (is_path and str(os.fspath(traj)).lower().endswith(".xtc")):
-                raise ValueError("box='file' reads the boxes of an .xtc path; pass the boxes as an array for any "
-                                 "other input")
-        elif box is not None:
-            box = _box_edges(box, "box")
-            if box.ndim == 1 and self.rmax > 0.5 * box.min():  # (a box a frame: run() knows which frames)
-                raise ValueError(f"range ends at {self.rmax}, over half the shortest box edge ({box.min()}): the "
-                                 "minimum image is not the only image in range")
-        elif norm == "rdf":
-            raise ValueError("norm='rdf' needs a box: free space has no volume (use norm='density' or 'none')")
+        box = _box_argument(box, traj)
+        if box is None:
+            if norm == "rdf":
+                raise ValueError("norm='rdf' needs a box: free space has no volume (use norm='density' or 'none')")
+        elif not isinstance(box, str) and box.ndim == 1 and self.rmax > 0.5 * box.min():
+            # (a box a frame: run() knows which frames)
+            raise ValueError(f"range ends at {self.rmax}, over half the shortest box edge ({box.min()}): the "
+                             "minimum image is not the only image in range")
         self.box = box
 
     def _boxes(self, n_traj: int, frames: np.ndarray):
         """f64 [len(frames), 3] for the run's frames; None in free space."""
-        box = self.box
-        if box is None:
-            return None
-        if isinstance(box, str):
-            from .xtc import XTCFile
-            with XTCFile(os.fspath(self._input)) as fh:
-                box = fh.boxes()
-        if box.ndim == 1:
-            return np.broadcast_to(box, (len(frames), 3)).copy()
-        if box.shape[0] != n_traj:
-            raise ValueError(f"box has {box.shape[0]} rows, the trajectory {n_traj} frames")
-        return np.ascontiguousarray(box[frames])
+        return _run_boxes(self.box, self._input, n_traj, frames)
 
     def run(self, start=None, stop=None, step=None, frames=None):
         self._refuse()

@@ -133,7 +133,43 @@ def main(argv=None) -> int:
     ap.add_argument("--rdf-select-b", default=None, metavar="SEL",
                     help="--rdf: the second group, a selection string read as --select is (natively read "
                          "topologies only)")
+    ap.add_argument("--msd", default=None, metavar="OUT.npz",
+                    help="also write the mean squared displacement of the selected atoms: delta_t_values, timeseries "
+                         "[n_lags] and msds_by_particle [n_lags, n] (rmsf_amd.EinsteinMSD; one process only).  "
+                         "With --msd-box the trajectory is unwrapped by the nojump rule first")
+    ap.add_argument("--msd-type", choices=["xyz", "xy", "yz", "xz", "x", "y", "z"], default=None,
+                    help="--msd: the coordinates of the displacement (default xyz)")
+    ap.add_argument("--msd-max-lag", type=int, default=None, metavar="L",
+                    help="--msd: the largest lag in frames (default: the number of frames less one)")
+    ap.add_argument("--msd-box", nargs="+", default=None, metavar="file|LX LY LZ",
+                    help="--msd: 'file' for the boxes of an .xtc trajectory, or three edges in A of one orthorhombic "
+                         "box, to unwrap the trajectory with (unwrap='nojump')")
+    ap.add_argument("--msd-dt", type=float, default=None, metavar="DT",
+                    help="--msd: the time between two frames, for delta_t_values (default 1)")
     a = ap.parse_args(argv)
+    msd_box = None
+    if not a.msd and (a.msd_type or a.msd_max_lag is not None or a.msd_box or a.msd_dt is not None):
+        ap.error("--msd-type, --msd-max-lag, --msd-box and --msd-dt need --msd OUT.npz")
+    if a.msd:
+        if int(os.environ.get("WORLD_SIZE", 1)) > 1:
+            ap.error("--msd runs in one process (no torch.distributed launch)")
+        if a.msd_max_lag is not None and a.msd_max_lag < 0:
+            ap.error("--msd-max-lag must not be negative")
+        if a.msd_max_lag is not None and a.synthetic and a.msd_max_lag >= a.synthetic[1]:
+            ap.error("--msd-max-lag must be below the number of frames")
+        if a.msd_dt is not None and not abs(a.msd_dt) < float("inf"):
+            ap.error("--msd-dt must be finite")
+        if a.msd_box == ["file"]:
+            if not (a.trajectory and a.trajectory.lower().endswith(".xtc")):
+                ap.error("--msd-box file needs an .xtc --trajectory")
+            msd_box = "file"
+        elif a.msd_box is not None:
+            try:
+                msd_box = [float(v) for v in a.msd_box]
+            except ValueError:
+                msd_box = []
+            if len(msd_box) != 3 or not all(0.0 < v < float("inf") for v in msd_box):
+                ap.error("--msd-box takes 'file' or three positive finite edges LX LY LZ")
     rdf_box = None
     if not a.rdf and (a.rdf_range or a.rdf_nbins is not None or a.rdf_box or a.rdf_select_b):
         ap.error("--rdf-range, --rdf-nbins, --rdf-box and --rdf-select-b need --rdf OUT.npz")
@@ -373,6 +409,19 @@ def main(argv=None) -> int:
               f"[{rd.edges[0]}, {rd.edges[-1]}] A: {int(rd.count_int.sum())} pair distances in range, the largest "
               f"value {np.nanmax(rd.rdf):.4f} at {rd.bins[int(np.nanargmax(rd.rdf))]:.3f} A", flush=True)
         np.savez(a.rdf, bins=rd.bins, edges=rd.edges, count=rd.count, rdf=rd.rdf, volume=rd.volume)
+    if a.msd:
+        from rmsf_amd import EinsteinMSD
+        msd_kw = {"select": dm_kw["select"]} if dm_kw else {}
+        if msd_box == "file" and not isinstance(dm_input, str):
+            raise SystemExit("--msd-box file reads the boxes through the native .xtc reader only")
+        ms = EinsteinMSD(dm_input, msd_type=a.msd_type or "xyz", max_lag=a.msd_max_lag,
+                         unwrap=None if msd_box is None else "nojump", box=msd_box,
+                         dt=1.0 if a.msd_dt is None else a.msd_dt, **msd_kw).run().results
+        print(f"mean squared displacement ({a.msd_type or 'xyz'}) of {ms.n_particles} atoms over {ms.n_frames} "
+              f"frames, {len(ms.timeseries)} lags: {ms.timeseries[-1]:.6f} A^2 at the largest"
+              + ("" if msd_box is None else ", unwrapped (nojump)"), flush=True)
+        np.savez(a.msd, delta_t_values=ms.delta_t_values, timeseries=ms.timeseries,
+                 msds_by_particle=ms.msds_by_particle)
     if a.tica:
         from rmsf_amd import TICA
         tica_kw = {"select": dm_kw["select"], "masses": dm_kw["weights"]} if dm_kw else {}
